@@ -56,6 +56,32 @@ def synthetic_batches(args, device, rank, n=2):
     return out
 
 
+DUMP_PARAM_SAMPLE = 1 << 22          # parameter values kept by --dump-outputs (16 MB of f32; the whole arena is ~625 MB at the default config)
+
+
+def dump_outputs(path, out, model):
+    """--dump-outputs: what a caller of the timed step receives after its last step, as DIR/<name>.npy (float32) — the loss and its
+    components, and the updated parameters as a fixed sample: sorted unique positions drawn with a fixed seed over the concatenation of
+    model.named_parameters() in their logical (torchvision / BERT) element order, so the sample does not depend on the arena's layout."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {"loss": out["loss"]}
+    arrays.update((k, v) for k, v in out["loss_components"].items() if k != "total_loss")
+    params = [p for _, p in model.named_parameters()]
+    sizes = torch.tensor([p.numel() for p in params], dtype=torch.int64)
+    starts = sizes.cumsum(0) - sizes
+    total = int(sizes.sum())
+    pos = torch.randint(0, total, (min(DUMP_PARAM_SAMPLE, total),), generator=torch.Generator().manual_seed(0)).unique()
+    owner = torch.searchsorted(starts, pos, right=True) - 1
+    parts = []
+    for i, sel in enumerate(torch.split(pos, torch.bincount(owner, minlength=len(params)).tolist())):
+        if sel.numel():
+            parts.append(params[i].detach().reshape(-1)[(sel - starts[i]).to(params[i].device)])
+    arrays["params_sample"] = torch.cat(parts)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
+
+
 CPU_BASELINE_SNIPPET = """
 import os, sys, time, json, torch
 sys.path.insert(0, {root!r}); sys.path.insert(0, os.path.join({root!r}, "tests"))
@@ -322,7 +348,11 @@ def main():
                     "direct mesh form for a fully connected xGMI node: all-to-all, local sum, all-gather (utils/distributed.py)")
     ap.add_argument("--force-exchange", action="store_true", help="run the gradient exchange (process group, RCCL all-reduces between the graphs) even with "
                     "one rank: exercises the data-parallel launch path on a one-GPU box (launch under torch.distributed.run)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed (loss, loss components, a fixed sample "
+                    "of the updated parameters) as DIR/<name>.npy in float32")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # stdout carries exactly one line, the JSON result: RCCL prints a version banner to fd 1 when the process group comes up (and the encoders
     # print construction banners), so fd 1 is pointed at stderr for the whole run and the result goes to the original stdout
@@ -408,6 +438,8 @@ def main():
         tdist.all_reduce(t, op=tdist.ReduceOp.MAX)
         dt = t.item()
     loss = out["loss"].item()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out, model)
     replicas_identical = None
     if dist_on:
         # data parallel keeps every rank's parameters bit-identical (same mean gradient, same update). A BITWISE comparison: integer sums of the

@@ -557,6 +557,39 @@ def test_bench_under_torchrun_with_rccl_exchange_one_rank():
 
 
 @pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_timed_step_and_reproducible(tmp_path):
+    """bench.py --dump-outputs DIR: after the timed steps (exactly --steps of them on the result line, with ms_per_step), the last step's loss —
+    the result line's value —, its components and the fixed sample of the updated parameters land as float32 .npy files, 64 MB at most in all.
+    The inputs are the same from run to run: two runs in the deterministic-reduction mode dump bit-identical arrays."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, CLITE_DETERMINISTIC="1")
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "3", "--batch", "16", "--visual", "resnet18",
+               "--layers", "2", "--no-cpu-baseline", "--no-side-records", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, r.stdout
+        res = json.loads(lines[0])
+        assert res["steps"] == 4 and res["ms_per_step"] > 0 and res["launch"] == "hipGraph replay"
+        files = sorted(os.listdir(d))
+        assert files == ["cross_modal_loss.npy", "loss.npy", "params_sample.npy", "textual_loss.npy", "visual_loss.npy"]
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        arrays = {f[:-4]: np.load(d / f) for f in files}
+        assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrays.values())
+        assert float(arrays["loss"]) == res["loss"]
+        assert arrays["params_sample"].size > 1_000_000
+        dumps.append(arrays)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("exchange", ["allreduce", "mesh"])
 def test_bench_two_ranks_keep_identical_parameters_through_captured_steps(exchange):
     """Two ranks (one process each, both on this box's single GPU: `--single-device`, so the process group is gloo — RCCL needs one GPU per
