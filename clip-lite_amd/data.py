@@ -296,3 +296,80 @@ class JsonCaptionDataset(_CaptionDataset):
     def caption(self, idx):
         c = self.records[idx]["caption"]
         return c[0] if isinstance(c, list) else c
+
+
+# ------------------------------------------------------------------------------------------------ downstream classification
+IMAGE_EXTENSIONS = (".jpg", ".jpeg", ".png", ".ppm", ".bmp", ".pgm", ".tif", ".tiff", ".webp")     # torchvision datasets.folder
+
+
+def _label_collate(items):
+    """reference data/dataloader.py ImageNetDataset.collate_fn: {"image": f32 [B][3][H][W], "label": int64 [B]}"""
+    return {"image": torch.stack([i["image"] for i in items], 0), "label": torch.stack([i["label"] for i in items], 0)}
+
+
+class ImageFolderDataset(Dataset):
+    """root/{train,val}/<class>/<image>: classes sorted by directory name into indices, images sorted inside a class (torchvision ImageFolder
+    order, behind the reference's ImageNetDataset / INaturalist2018Dataset). `percentage` < 100 keeps the first K % of every class on the
+    train split only (reference data/dataloader.py:986-995). Images go through `load_image` with the reference's transform names; random
+    transforms draw from a generator seeded by (seed, index)."""
+
+    def __init__(self, data_root: str, split: str = "train", image_transform=DEFAULT_IMAGE_TRANSFORM, image_size: int = 224,
+                 percentage: float = 100.0, seed: int = 0):
+        if percentage <= 0:
+            raise ValueError("Cannot load dataset with 0 percent original size.")
+        self.root = os.path.join(data_root, split)
+        if not os.path.isdir(self.root):
+            raise FileNotFoundError(f"image folder split not found: {self.root} (expected <root>/{split}/<class>/<image>)")
+        self.classes = sorted(d.name for d in os.scandir(self.root) if d.is_dir())
+        if not self.classes:
+            raise FileNotFoundError(f"no class directories under {self.root}")
+        self.class_to_idx = {c: i for i, c in enumerate(self.classes)}
+        self.samples = []
+        for c in self.classes:
+            files = sorted(f for f in os.listdir(os.path.join(self.root, c)) if f.lower().endswith(IMAGE_EXTENSIONS))
+            if split == "train" and percentage < 100:
+                files = files[:int(len(files) * (percentage / 100))]
+            self.samples += [(os.path.join(self.root, c, f), self.class_to_idx[c]) for f in files]
+        self.targets = [t for _, t in self.samples]
+        self.image_transform, self.image_size, self.seed = tuple(image_transform), image_size, seed
+
+    @property
+    def num_classes(self):
+        return len(self.classes)
+
+    def __len__(self):
+        return len(self.samples)
+
+    def __getitem__(self, idx):
+        path, label = self.samples[idx]
+        g = torch.Generator().manual_seed(self.seed * 1000003 + idx)
+        return {"image": load_image(path, self.image_transform, self.image_size, g), "label": torch.tensor(label, dtype=torch.long)}
+
+    collate_fn = staticmethod(_label_collate)
+
+
+class RandomLabelledDataset(Dataset):
+    """Synthetic labelled images (DATA.ROOT "random"): image = N(0, 1) noise + `strength` x a fixed random pattern of its class, so a linear
+    probe on a random backbone can learn it. Every index is reproducible (seeded by split, seed and index); the class patterns depend on
+    `seed` only, so train and val share them."""
+
+    def __init__(self, num_classes: int = 10, image_size: int = 224, length: int = 50000, split: str = "train", seed: int = 0, strength: float = 1.0):
+        self.num_classes, self.image_size, self.length, self.strength = num_classes, image_size, length, strength
+        self.seed = seed * 2 + (0 if split == "train" else 1)
+        g = torch.Generator().manual_seed(seed * 7919 + 17)
+        self.patterns = torch.randn(num_classes, 3, image_size, image_size, generator=g)
+        self.classes = [f"class_{i}" for i in range(num_classes)]
+
+    def __len__(self):
+        return self.length
+
+    def label(self, idx):
+        return (idx * 7 + self.seed) % self.num_classes
+
+    def __getitem__(self, idx):
+        g = torch.Generator().manual_seed(self.seed * 1000003 + idx)
+        y = self.label(idx)
+        image = torch.randn(3, self.image_size, self.image_size, generator=g) + self.strength * self.patterns[y]
+        return {"image": image, "label": torch.tensor(y, dtype=torch.long)}
+
+    collate_fn = staticmethod(_label_collate)

@@ -1,0 +1,214 @@
+"""Command lines of the downstream evaluations: `linear_clf.py` (linear probe / fine-tune, reference linear_clf.py:25-300) and `zero_shot.py`
+(reference zero_shot.py), on ImageClassifier / zero_shot_counts (classify.py). One GPU: the reference's multi-GPU launch, hipGraph capture of the
+classification step, and the `clip` / `imagenet` initialisations (the `clip` package, torchvision downloads) are not available."""
+import argparse
+import os
+
+import torch
+from torch.utils.data import DataLoader, DistributedSampler
+
+from .classify import ImageClassifier, TopkAccuracy, cross_entropy, zero_shot_counts
+from .config import Config
+from .factories import DownstreamDatasetFactory, LRSchedulerFactory, OptimizerFactory, PretrainingModelFactory
+from .utils.base import Timer
+from .utils.checkpointing import CheckpointManager
+from .utils.common import common_parser, common_setup, cycle, logger
+
+
+def build_linear_clf_parser():
+    parser = common_parser(description="Do image classification with linear models and frozen feature extractor, or fine-tune the feature "
+                                       "extractor end-to-end.")
+    parser.set_defaults(num_gpus_per_machine=1)
+    group = parser.add_argument_group("Downstream config arguments.")
+    group.add_argument("--down-config", metavar="FILE", help="Path to a downstream config file.")
+    group.add_argument("--down-config-override", nargs="*", default=[], help="A list of key-value pairs to modify downstream config params.")
+    group = parser.add_argument_group("Checkpointing and Logging")
+    group.add_argument("--weight-init", choices=["random", "imagenet", "torchvision", "vlinfo", "clip"], default="vlinfo",
+                       help="'random': random weights; 'vlinfo': the backbone of a pretraining checkpoint (--checkpoint-path). 'imagenet', "
+                            "'torchvision' and 'clip' are not supported (downloads, the clip package); resume a run of this script with --resume-from.")
+    group.add_argument("--log-every", type=int, default=500, help="Log the training loss after every these many iterations.")
+    group.add_argument("--checkpoint-path", help="Checkpoint to initialise from (vlinfo: a pretraining checkpoint).")
+    group.add_argument("--checkpoint-every", type=int, default=10000, help="Validate and serialize after every these many iterations.")
+    group.add_argument("--resume-from", type=str, default=None, help="Resume training from a checkpoint of this script.")
+    group.add_argument("--serialization-dir", default=None, help="Where checkpoints go (default: <checkpoint-path dir>/<dataset>, or "
+                                                                 "<checkpoints-dir><RUN_ID> without a checkpoint path).")
+    return parser
+
+
+def _check_launch(_A):
+    if _A.num_gpus_per_machine > 1 or _A.num_machines > 1:
+        raise SystemExit("linear_clf: runs on one GPU (--num-gpus-per-machine 1); multi-GPU data parallelism of the classification step is "
+                         "not implemented")
+    if _A.num_gpus_per_machine == 0:
+        raise SystemExit("linear_clf: the classification kernels run on the MI355X only; there is no CPU path (--num-gpus-per-machine 1)")
+
+
+def _check_init(_A):
+    if _A.weight_init in ("imagenet", "torchvision", "clip"):
+        need = {"imagenet": "torchvision model-zoo downloads", "torchvision": "torchvision's classification training checkpoints",
+                "clip": "the clip package"}[_A.weight_init]
+        raise SystemExit(f"linear_clf: --weight-init {_A.weight_init} needs {need}, which is not supported here; use random or vlinfo")
+    if _A.weight_init == "vlinfo" and not _A.checkpoint_path:
+        raise SystemExit(f"linear_clf: --weight-init {_A.weight_init} needs --checkpoint-path")
+
+
+def build_classifier(_A, _C, _DOWNC, num_classes):
+    frozen, amp = _DOWNC.MODEL.VISUAL.FROZEN, _DOWNC.AMP
+    if _A.weight_init == "vlinfo":
+        ckpt = torch.load(_A.checkpoint_path, map_location="cpu", weights_only=False)
+        model = ImageClassifier.from_pretraining(ckpt, _C.MODEL.VISUAL.NETWORK_NAME, num_classes, frozen, amp)
+    else:
+        model = ImageClassifier(_DOWNC.MODEL.VISUAL.NETWORK_NAME, num_classes, frozen, amp)
+    if model.out_dim != _DOWNC.MODEL.VISUAL.FEATURE_SIZE:
+        raise ValueError(f"MODEL.VISUAL.FEATURE_SIZE {_DOWNC.MODEL.VISUAL.FEATURE_SIZE} != the {model.visual_name} feature size {model.out_dim}")
+    return model
+
+
+def linear_clf_main(_A):
+    _check_launch(_A)
+    _check_init(_A)
+    if not torch.cuda.is_available():
+        raise SystemExit("linear_clf: no GPU visible; the classification kernels run on the MI355X only")
+    device = torch.device("cuda", torch.cuda.current_device())
+    _DOWNC = Config(_A.down_config, _A.down_config_override)
+    common_setup(_DOWNC, _A, job_type="downstream")
+    _C = Config(_A.config, _A.config_override)
+    DATASET = DownstreamDatasetFactory.dataset_name(_DOWNC.DATA.ROOT)
+
+    train_dataset = DownstreamDatasetFactory.from_config(_DOWNC, split="train")
+    val_dataset = DownstreamDatasetFactory.from_config(_DOWNC, split="val")
+    NUM_CLASSES = train_dataset.num_classes
+    bs = _DOWNC.OPTIM.BATCH_SIZE
+    train_dataloader = DataLoader(train_dataset, batch_size=bs, num_workers=_A.cpu_workers,
+                                  sampler=DistributedSampler(train_dataset, num_replicas=1, rank=0, shuffle=True), drop_last=False,
+                                  pin_memory=True, collate_fn=train_dataset.collate_fn)
+    val_dataloader = DataLoader(val_dataset, batch_size=bs, num_workers=_A.cpu_workers,
+                                sampler=DistributedSampler(val_dataset, num_replicas=1, rank=0, shuffle=False), drop_last=False,
+                                pin_memory=True, collate_fn=val_dataset.collate_fn)
+
+    model = build_classifier(_A, _C, _DOWNC, NUM_CLASSES).to(device)
+    frozen = _DOWNC.MODEL.VISUAL.FROZEN
+    if frozen:
+        model.eval()
+    top1 = TopkAccuracy(top_k=1)
+    optimizer = OptimizerFactory.from_config(_DOWNC, model.named_parameters())
+    scheduler = LRSchedulerFactory.from_config(_DOWNC, optimizer)
+
+    start_iteration = 0
+    if _A.resume_from is not None:
+        start_iteration = max(0, CheckpointManager(model=model, optimizer=optimizer, scheduler=scheduler).load(_A.resume_from))
+    if _A.serialization_dir:
+        serialization_dir = _A.serialization_dir
+    elif _A.checkpoint_path:
+        serialization_dir = os.path.join(os.path.dirname(_A.checkpoint_path), DATASET)
+    else:
+        serialization_dir = _A.checkpoints_dir + _DOWNC.RUN_ID
+    os.makedirs(serialization_dir, exist_ok=True)
+    checkpoint_manager = CheckpointManager(serialization_dir, model=model, optimizer=optimizer, scheduler=scheduler)
+
+    timer = Timer(start_from=start_iteration, total_iterations=_DOWNC.OPTIM.NUM_ITERATIONS)
+    train_iter = cycle(train_dataloader, device, start_iteration)
+    for iteration in range(start_iteration + 1, _DOWNC.OPTIM.NUM_ITERATIONS + 1):
+        timer.tic()
+        optimizer.zero_grad()
+        batch = next(train_iter)
+        logits = model(batch["image"])
+        loss = cross_entropy(logits, batch["label"])
+        loss.backward()
+        optimizer.step()
+        scheduler.step()
+        timer.toc()
+        if iteration % _A.log_every == 0:
+            logger.info(f"{timer.stats} | Loss: {loss.item():.3f}")
+
+        if iteration % _A.checkpoint_every == 0:
+            torch.set_grad_enabled(False)
+            model.eval()
+            total_val_loss = torch.zeros((), device=device)
+            n_val = 0
+            for batch in val_dataloader:
+                logits = model(batch["image"].to(device, non_blocking=True))
+                labels = batch["label"].to(device, non_blocking=True)
+                total_val_loss += cross_entropy(logits, labels)
+                top1(logits, labels)
+                n_val += 1
+            total_val_loss = total_val_loss / max(n_val, 1)
+            acc = top1.get_metric(reset=True)
+            torch.set_grad_enabled(True)
+            if not frozen:                     # back to train mode only when fine-tuning end to end (reference linear_clf.py:280-282)
+                model.train()
+            checkpoint_manager.step(iteration)
+            logger.info(f"Iter: {iteration} | Val loss: {total_val_loss.item():.4f} | Top-1 accuracy: {acc}")
+    return model
+
+
+def linear_clf_cli(argv=None):
+    _A = build_linear_clf_parser().parse_args(argv)
+    return linear_clf_main(_A)
+
+
+# ------------------------------------------------------------------------------------------------ zero-shot
+def build_zero_shot_parser():
+    parser = argparse.ArgumentParser(description="Zero-shot image classification with a pretrained model: class prompts through the text "
+                                                 "encoder, each image assigned to the prompt of highest cosine (reference zero_shot.py).")
+    parser.add_argument("--config", metavar="FILE", help="Path to the pretraining config file.")
+    parser.add_argument("--config-override", nargs="*", default=[], help="A list of key-value pairs to modify pretraining config params.")
+    parser.add_argument("--checkpoint-path", required=True, help="Pretraining checkpoint to evaluate.")
+    parser.add_argument("--data-root", required=True, help="Image folder root/val/<class>/<image>, or 'random' for the synthetic source.")
+    parser.add_argument("--prompt", default="a picture of a {}.", help="Prompt template; {} is replaced by the class name (reference "
+                                                                      "zero_shot.py:74-85).")
+    parser.add_argument("--max-length", type=int, default=30, help="Prompt token length (padded).")
+    parser.add_argument("--batch-size", type=int, default=128)
+    parser.add_argument("--cpu-workers", type=int, default=2)
+    parser.add_argument("--num-gpus-per-machine", type=int, default=1, help="Only 1 is supported.")
+    return parser
+
+
+def tokenize_prompts(names, template, max_length, vocab=""):
+    """(input_ids, attention_mask) int64 [C][max_length] of template.format(name) for every class, padded with 0 (padding="max_length",
+    truncation=True, reference zero_shot.py:104-110). The project's WordPiece tokenizer when a vocabulary file is configured."""
+    from .data import WordPieceTokenizer, hash_tokenize, normalize_caption
+    tok = WordPieceTokenizer(vocab) if vocab else None
+    ids = torch.zeros(len(names), max_length, dtype=torch.long)
+    mask = torch.zeros(len(names), max_length, dtype=torch.long)
+    for i, name in enumerate(names):
+        text = template.format(name.replace("_", " "))
+        t = tok(normalize_caption(text, max_length), max_length) if tok is not None else hash_tokenize(text, max_length)
+        t = list(t)[:max_length]
+        ids[i, :len(t)] = torch.tensor(t, dtype=torch.long)
+        mask[i, :len(t)] = 1
+    return ids, mask
+
+
+def zero_shot_main(_A):
+    if _A.num_gpus_per_machine != 1:
+        raise SystemExit("zero_shot: runs on one GPU (--num-gpus-per-machine 1)")
+    if not torch.cuda.is_available():
+        raise SystemExit("zero_shot: no GPU visible; the kernels run on the MI355X only")
+    from . import retrieval
+    from .data import ImageFolderDataset, RandomLabelledDataset
+    device = torch.device("cuda", torch.cuda.current_device())
+    _C = Config(_A.config, _A.config_override)
+    model = PretrainingModelFactory.from_config(_C)
+    CheckpointManager(model=model).load(_A.checkpoint_path)
+    model = model.to(device).eval()
+    size = _C.DATA.IMAGE_CROP_SIZE
+    if _A.data_root == "random":
+        ds = RandomLabelledDataset(image_size=size, length=500, split="val", seed=_C.RANDOM_SEED)
+    else:
+        ds = ImageFolderDataset(_A.data_root, "val", tuple(_C.DATA.IMAGE_TRANSFORM_VAL), size)
+    ids, mask = tokenize_prompts(ds.classes, _A.prompt, _A.max_length, _C.DATA.TOKENIZER_VOCAB)
+    text = retrieval.embed_texts(model, ids.to(device), mask.to(device), _A.batch_size)
+    acc = torch.zeros(4, device=device)
+    loader = DataLoader(ds, batch_size=_A.batch_size, shuffle=False, num_workers=_A.cpu_workers, collate_fn=ds.collate_fn)
+    for batch in loader:
+        zero_shot_counts(model, text, batch["image"], batch["label"], acc, 5, _A.batch_size)
+    a = acc.tolist()
+    n = max(a[3], 1e-12)
+    res = {"top1": 100.0 * a[1] / n, "top5": 100.0 * a[2] / n}
+    print(f"zero-shot top-1: {res['top1']:.2f} | top-5: {res['top5']:.2f} ({int(a[3])} images, {len(ds.classes)} classes)")
+    return res
+
+
+def zero_shot_cli(argv=None):
+    return zero_shot_main(build_zero_shot_parser().parse_args(argv))

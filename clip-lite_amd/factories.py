@@ -53,6 +53,39 @@ class PretrainingDatasetFactory(Factory):
         return cls.create(_C.MODEL.NAME, **kwargs)
 
 
+class DownstreamDatasetFactory(Factory):
+    """Labelled image sources of the downstream classification evaluation (reference factories.py:534-596, linear_clf.py): DATA.ROOT "random"
+    is the synthetic RandomLabelledDataset; any other root is an image folder root/{train,val}/<class>/<image> (ImageFolderDataset, the
+    layout of the reference's ImageNetDataset / INaturalist2018Dataset). VOC2007 (voc_clf.py: sklearn SVMs) and detection (voc_det.py:
+    detectron2) need libraries that are not available."""
+    PRODUCTS: Dict[str, Callable] = {"random": vdata.RandomLabelledDataset, "folder": vdata.ImageFolderDataset}
+    # reference linear_clf.py:105 (the dataset name is the last path component of DATA.ROOT; "imagenet2012" means "imagenet")
+    NUM_CLASSES_MAPPING = {"imagenet": 1000, "inaturalist": 8142}
+
+    @staticmethod
+    def dataset_name(root: str) -> str:
+        name = root.rstrip("/").split("/")[-1]
+        return "imagenet" if name == "imagenet2012" else name
+
+    @classmethod
+    def from_config(cls, config: Config, split: str = "train"):
+        _C = config
+        root = _C.DATA.ROOT
+        if "voc" in cls.dataset_name(root).lower():
+            raise NotImplementedError("VOC2007 classification (reference voc_clf.py) trains sklearn SVMs and detection (voc_det.py) needs detectron2; "
+                                      "neither is available")
+        if root == "random":
+            return cls.create("random", image_size=_C.DATA.IMAGE_CROP_SIZE, length=50000 if split == "train" else 500, split=split,
+                              seed=_C.RANDOM_SEED)
+        transform = tuple(_C.DATA.IMAGE_TRANSFORM_TRAIN if "train" in split else _C.DATA.IMAGE_TRANSFORM_VAL)
+        ds = cls.create("folder", data_root=root, split=split, image_transform=transform, image_size=_C.DATA.IMAGE_CROP_SIZE,
+                        percentage=_C.DATA.USE_PERCENTAGE, seed=_C.RANDOM_SEED)
+        want = cls.NUM_CLASSES_MAPPING.get(cls.dataset_name(root))
+        if want is not None and ds.num_classes != want:
+            raise ValueError(f"{root}/{split} has {ds.num_classes} class directories; {cls.dataset_name(root)} has {want}")
+        return ds
+
+
 class VisualBackboneFactory(Factory):
     PRODUCTS: Dict[str, Callable] = {"captions": ImageEncoder, "random": ImageEncoder, "json": ImageEncoder}
 

@@ -142,6 +142,8 @@ _SIGNATURES = {
     "clite_l2_normalize_bwd": [_I, _V, _V, _V, _V, _I, _I, _V],
     "clite_infonce_fwd": [_V, _I, _I, _V, _V, _V, _V, _V],
     "clite_infonce_bwd": [_I, _V, _I, _I, _V, _V, _V, _V, _F, _V, _I, _V, _V],
+    "clite_xent_fwd": [_V, _I, _I, _I, _V, _I, _V, _V, _V],
+    "clite_xent_bwd": [_I, _V, _I, _I, _I, _I, _V, _V, _V, _V, _V, _I, _V],
     "clite_critic_jsd_bwd": [_I, _V, _V, _V, _V, _V, _F, _I, _I, _V, _V, _V, _V, _V, _V],
     "clite_prior_tail_fwd": [_I, _V, _V, _V, _I, _I, _I, _V, _V, _V],
     "clite_prior_tail_bwd": [_I, _V, _V, _V, _V, _F, _I, _I, _V, _V, _V, _V],
@@ -829,6 +831,15 @@ def infonce_fwd(Cm, ld, B, temperature, lse_r, lse_c, acc):
 
 def infonce_bwd(dt, Cm, ld, B, temperature, lse_r, lse_c, gout, scale, dC, ldd, dtemp):
     check(lib().clite_infonce_bwd(dt, p(Cm), ld, B, p(temperature), p(lse_r), p(lse_c), p(gout), scale, p(dC), ldd, p(dtemp), stream_ptr(Cm)), "infonce_bwd")
+
+
+def xent_fwd(logits, ld, B, C, labels, topk, lse, acc):
+    """lse[i] = logsumexp of row i; acc (f32[4]) += {sum loss, #top-1, #top-k, #counted rows} (include/clite.h: clite_xent_fwd)."""
+    check(lib().clite_xent_fwd(p(logits), ld, B, C, p(labels), topk, p(lse), p(acc), stream_ptr(logits)), "xent_fwd")
+
+
+def xent_bwd(dt, logits, ld, B, Bp, C, lse, labels, acc, gout, dlogits, ldd):
+    check(lib().clite_xent_bwd(dt, p(logits), ld, B, Bp, C, p(lse), p(labels), p(acc), p(gout), p(dlogits), ldd, stream_ptr(logits)), "xent_bwd")
 
 
 def critic_jsd_bwd(dt, f1, f2, temperature, work, gout, scale, B, D, df1, df2, dtemp, neg=None, neg_inv=None):

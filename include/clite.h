@@ -505,6 +505,20 @@ int clite_add(int dtype, const void* a, const void* b, void* out, uint64_t n, vo
 /* torch.rand_like replacement for the prior noise (loss.py:189,196): U[0,1) from Philox(seed, site, index). n % 8 == 0. */
 int clite_uniform_fill(int dtype, void* out, uint64_t n, uint64_t seed, uint32_t site, void* stream);
 
+/* ---- Downstream classification (reference linear_clf.py, zero_shot.py; clip-lite_amd/classify.py). One wave per row of f32 logits [B][ld]
+ * (ld % 4 == 0, ld >= C, 16-byte aligned), C >= 1 real classes; labels int64 [B]. A label of -100 (torch's ignore_index) — or any value outside
+ * [0, C) — adds nothing to the loss or the count.
+ * lse (f32 [B]) = logsumexp over the C columns, kept for backward. acc (f32 [4], accumulated: zero it first, or keep adding across batches)
+ * += { sum (lse - z_y), #[rank == 0], #[rank < topk], #counted rows } with rank = #{j: z_j > z_y} + #{j < y: z_j == z_y} (ties go to the lower index).
+ * Replaces nn.CrossEntropyLoss at linear_clf.py:188, TopkAccuracy at utils/metrics.py:20-73 and torch.max at zero_shot.py:155.
+ * Deterministic mode: one wave over all rows in order, one contribution per accumulator. */
+int clite_xent_fwd(const float* logits, int ld, int B, int C, const int64_t* labels, int topk, float* lse, float* acc, void* stream);
+/* dlogits (call dtype, [Bp][ldd], ldd % 8 == 0, ldd >= C, Bp >= B) = gout / acc[3] * (softmax(z_i) - onehot(y_i)) — the gradient of the mean over the
+ * counted rows, autograd of linear_clf.py:188; zeros in columns >= C, rows >= B and ignored rows. gout (f32 scalar) and the count are read on the
+ * device. A batch with no counted row gets a zero gradient. */
+int clite_xent_bwd(int dtype, const float* logits, int ld, int B, int Bp, int C, const float* lse, const int64_t* labels, const float* acc,
+                   const float* gout, void* dlogits, int ldd, void* stream);
+
 /* ---- Update path (reference train.py:221-226, factories.py:464-482, optim/lookahead.py:88-101) over flat f32 buffers. */
 typedef struct clite_optim_item {   /* one workgroup's slice of one parameter tensor (never straddles tensors) */
   uint64_t start;                   /* element offset into the flat buffers, multiple of 4 */
