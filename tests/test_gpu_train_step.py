@@ -590,13 +590,39 @@ def test_bench_dump_outputs_are_the_last_timed_step_and_reproducible(tmp_path):
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_and_full_adds_the_roofline():
+    """A plain bench.py run carries the headline fields and nothing that needs work of its own; --full adds the per-launch roofline pass
+    (its instrumented eager steps time the implicit-GEMM launches) and keeps the headline fields."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "3", "--batch", "16", "--visual", "resnet18",
+            "--layers", "2"]
+    lines = {}
+    for name, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline"])):
+        r = subprocess.run(base + extra, cwd=root, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = [l for l in r.stdout.splitlines() if l.strip()]
+        assert len(out) == 1, r.stdout
+        lines[name] = json.loads(out[0])
+    for res in lines.values():
+        assert res["steps"] == 3 and res["warmup"] == 3 and res["ms_per_step"] > 0 and res["value"] > 0 and res["unit"] == "pairs/s"
+        assert res["higher_is_better"] is True and res["dtype"] == "bf16" and res["launch"] == "hipGraph replay" and np.isfinite(res["loss"])
+    assert not {"roofline", "cpu_baseline", "replicas_identical", "bs1024_single_gpu", "f32_parity_mode", "f32_exact_mode"} & set(lines["plain"])
+    roof = lines["full"]["roofline"]
+    assert roof["launches_per_step"] > 0 and roof["kernel_ms_per_step"] > 0 and roof["launched_flops"] > 0
+    assert "cpu_baseline" not in lines["full"]
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("exchange", ["allreduce", "mesh"])
 def test_bench_two_ranks_keep_identical_parameters_through_captured_steps(exchange):
     """Two ranks (one process each, both on this box's single GPU: `--single-device`, so the process group is gloo — RCCL needs one GPU per
     rank) run bench.py's captured data-parallel step: per-phase hipGraphs with the gradient-region exchanges (RCCL-style all-reduce, or the
     mesh form: all-to-all + clite_sum_slices + all-gather) issued between them
     (train_loop.TrainStep._replay_direct), different synthetic shards per rank. After warm-up + 5 replayed steps every rank's parameter
-    arena must be bit-identical (bench.py compares a 64-bit checksum across ranks: `replicas_identical`), i.e. each rank applied the same
+    arena must be bit-identical (bench.py --full compares a 64-bit checksum across ranks: `replicas_identical`), i.e. each rank applied the same
     mean gradient (reference train.py:174-178)."""
     import json
     import subprocess
@@ -605,7 +631,7 @@ def test_bench_two_ranks_keep_identical_parameters_through_captured_steps(exchan
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29541",
            os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "3", "--batch", "16", "--visual", "resnet18", "--layers", "2",
-           "--backend", "gloo", "--single-device", "--no-cpu-baseline", "--exchange", exchange]
+           "--backend", "gloo", "--single-device", "--full", "--no-cpu-baseline", "--exchange", exchange]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]

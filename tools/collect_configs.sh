@@ -7,7 +7,7 @@ set -e
 cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/r5c
 mkdir -p $O
-B="--no-cpu-baseline --no-side-records --steps 12 --warmup 3"
+B="--full --no-cpu-baseline --no-side-records --steps 12 --warmup 3"
 V=build/varf8/libclite_hip_var.so
 python bench.py $B --visual resnet101 --batch 256 > $O/r5_bench_rn101_b256.json 2> $O/err.log
 python bench.py $B --visual resnet101 --batch 256 --fp8 > $O/r5_bench_rn101_b256_fp8.json 2>> $O/err.log

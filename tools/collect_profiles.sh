@@ -16,7 +16,7 @@ cp $O/r5_hbm_traffic.json profiles/r5_hbm_traffic.json
 rocprofv3 --kernel-trace -d $O/kt -o kt -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-side-records > $O/kt.log 2>&1
 python tools/rocpd_stats.py $O/kt/kt_results.db $O/r5_kernel_stats.csv $O/r5_kernel_stats.json
 cp $O/r5_kernel_stats.json profiles/r5_kernel_stats.json
-python bench.py > $O/r5_bench.json 2> $O/bench.err
+python bench.py --full > $O/r5_bench.json 2> $O/bench.err
 python tools/diag_launch.py > $O/r5_timeline.txt 2>&1
 python tools/layer_profile.py > $O/r5_layers.txt 2> $O/layers.err
 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES -d $O/pmc_m -o m -- python3 bench.py --steps 2 --warmup 2 --no-graph --no-cpu-baseline > $O/pmc_m.log 2>&1

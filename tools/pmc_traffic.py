@@ -8,7 +8,7 @@ The output records the date and bench.kernel_source_hash() (sha256 over csrc/, i
 `roofline.traffic` only while that hash matches the tree it runs from, so a kernel change without new PMC passes yields null, not a stale number.
 
 Both counters are reported in KiB; FETCH_SIZE is doubled (gfx950 tallies 64 B per 128-B request, MI355X_MICROARCH.md). Steps are counted by
-the update kernel's dispatches (one per step); bench.py's per-launch roofline pass runs extra eager steps, which are steps like any other."""
+the update kernel's dispatches (one per step); with --full, bench.py's per-launch roofline pass adds eager steps, which are steps like any other."""
 import datetime
 import json
 import os

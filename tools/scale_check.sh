@@ -9,7 +9,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 export HSA_ENABLE_IPC_MODE_LEGACY=0
 mkdir -p gpurun_out
 for ex in allreduce mesh; do
-  python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29547 bench.py --gpus 2 --steps 5 --warmup 3 \
+  python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29547 bench.py --gpus 2 --steps 5 --warmup 3 --full \
     --backend gloo --single-device --no-cpu-baseline --exchange $ex > gpurun_out/scale_check_$ex.json 2> gpurun_out/scale_check_$ex.err
   python - "$ex" <<'PY'
 import json, math, sys
