@@ -373,3 +373,45 @@ class RandomLabelledDataset(Dataset):
         return {"image": image, "label": torch.tensor(y, dtype=torch.long)}
 
     collate_fn = staticmethod(_label_collate)
+
+
+class VOC07ClassificationDataset(Dataset):
+    """PASCAL VOC 2007 image-label pairs (reference data/dataloader.py:800-882): classes are the sorted `ImageSets/Main/<class>_<split>.txt`
+    files; each line "<image> <label>" maps VOC 1 -> 1 (present), -1 -> 0 (absent), 0 -> -1 (difficult); an image missing from a class file
+    keeps -1 there. Instances come in order of first appearance while reading the sorted class files; images are JPEGImages/<name>.jpg through
+    `load_image` with the reference's transform names (random ones seeded by (seed, index), like ImageFolderDataset).
+    Items: {"image": f32 [3][H][W], "label": int64 [K]}."""
+
+    def __init__(self, data_root: str, split: str = "trainval", image_transform=DEFAULT_IMAGE_TRANSFORM, image_size: int = 224, seed: int = 0):
+        import glob
+        ann_paths = sorted(glob.glob(os.path.join(data_root, "ImageSets", "Main", f"*_{split}.txt")))
+        if not ann_paths:
+            raise FileNotFoundError(f"no VOC class files {data_root}/ImageSets/Main/*_{split}.txt")
+        self.split = split
+        self.class_names = [os.path.basename(p).split("_")[0] for p in ann_paths]
+        labels = {}
+        for k, path in enumerate(ann_paths):
+            with open(path) as f:
+                for line in f:
+                    if not line.strip():
+                        continue
+                    name, orig = line.split()
+                    orig = int(orig)
+                    lab = labels.setdefault(name, [-1] * len(ann_paths))
+                    lab[k] = 0 if orig == -1 else -1 if orig == 0 else 1
+        self.instances = [(os.path.join(data_root, "JPEGImages", f"{name}.jpg"), lab) for name, lab in labels.items()]
+        self.image_transform, self.image_size, self.seed = tuple(image_transform), image_size, seed
+
+    @property
+    def num_classes(self):
+        return len(self.class_names)
+
+    def __len__(self):
+        return len(self.instances)
+
+    def __getitem__(self, idx):
+        path, label = self.instances[idx]
+        g = torch.Generator().manual_seed(self.seed * 1000003 + idx)
+        return {"image": load_image(path, self.image_transform, self.image_size, g), "label": torch.tensor(label, dtype=torch.long)}
+
+    collate_fn = staticmethod(_label_collate)

@@ -212,3 +212,117 @@ def zero_shot_main(_A):
 
 def zero_shot_cli(argv=None):
     return zero_shot_main(build_zero_shot_parser().parse_args(argv))
+
+
+# ------------------------------------------------------------------------------------------------ VOC07 SVMs
+def build_voc_clf_parser():
+    parser = common_parser(description="Train SVMs for VOC2007 classification on a pretrained model.")
+    parser.set_defaults(num_gpus_per_machine=1)
+    group = parser.add_argument_group("Downstream config arguments.")
+    group.add_argument("--down-config", metavar="FILE", help="Path to a downstream config file.")
+    group.add_argument("--down-config-override", nargs="*", default=[], help="A list of key-value pairs to modify downstream config params.")
+    group = parser.add_argument_group("Checkpointing")
+    group.add_argument("--weight-init", choices=["random", "imagenet", "torchvision", "vlinfo"], default="vlinfo",
+                       help="'random': random weights for the first evaluation; 'vlinfo': checkpoint_<start-iter>.pth of --checkpoint-dir. "
+                            "'imagenet' and 'torchvision' (model-zoo downloads) are not supported.")
+    group.add_argument("--loss-type", choices=["dot", "concat"], default="dot", help="Which MI estimation approach has been used?")
+    group.add_argument("--checkpoint-dir", required=True, help="Path to load checkpoints from and write voc07_mAP.txt to.")
+    group.add_argument("--freq", type=int, default=46200, help="Evaluate every these many iterations.")
+    group.add_argument("--start-iter", type=int, default=46200, help="First iteration to evaluate.")
+    return parser
+
+
+def _check_voc_launch(_A):
+    if _A.num_gpus_per_machine == 0:
+        raise SystemExit("voc_clf: feature extraction and the SVM solver run on the MI355X only; there is no CPU path (--num-gpus-per-machine 1)")
+    if _A.num_gpus_per_machine > 1 or _A.num_machines > 1:
+        raise SystemExit("voc_clf: runs on one GPU (--num-gpus-per-machine 1)")
+    if _A.weight_init in ("imagenet", "torchvision"):
+        raise SystemExit(f"voc_clf: --weight-init {_A.weight_init} needs torchvision model-zoo downloads, which are not supported here; use random "
+                         "or vlinfo")
+
+
+def checkpoint_path(checkpoint_dir: str, iteration: int) -> str:
+    return os.path.join(checkpoint_dir, f"checkpoint_{iteration}.pth")
+
+
+def run_checkpoint_loop(checkpoint_dir, start_iter, freq, evaluate, load):
+    """Reference voc_clf.py:218-237: evaluate (-> mAP as a fraction), print it, merge {iteration: mAP x 100} into <checkpoint_dir>/voc07_mAP.txt
+    (JSON), then load checkpoint_<iteration + freq>.pth and go on until that load fails ("Completed!"). Returns the merged results."""
+    import json
+    out = os.path.join(checkpoint_dir, "voc07_mAP.txt")
+    results = {}
+    if os.path.exists(out):
+        with open(out) as f:
+            results = json.load(f)
+    it = int(start_iter)
+    while True:
+        test_map = evaluate()
+        print("Test mAP: " + str(test_map * 100))
+        results[str(it)] = test_map * 100
+        with open(out, "w") as f:
+            json.dump(results, f)
+        it += int(freq)
+        try:
+            load(checkpoint_path(checkpoint_dir, it))
+        except Exception:
+            print("Completed!")
+            return results
+
+
+@torch.no_grad()
+def extract_features(model, loader, device):
+    """(features f32 [N][F], targets int [N][K]) in dataset order: the pretraining model's image encoder in eval mode, then clite_l2_normalize
+    (reference voc_clf.py:171-200: pooled features / their L2 norm). The encoder's compute dtype is the model's (AMP: bf16, else exact f32)."""
+    from . import hip
+    enc = model.image_encoder
+    was = enc.training
+    enc.eval()
+    feats, tgts = [], []
+    for batch in loader:
+        f = enc(batch["image"].to(device)).contiguous()
+        o = torch.empty_like(f)
+        hip.l2_normalize(model.runtime.dt, f, o, f.shape[0], f.shape[1])
+        feats.append(o.float())
+        tgts.append(batch["label"])
+    enc.train(was)
+    return torch.cat(feats, 0), torch.cat(tgts, 0)
+
+
+def voc_clf_main(_A):
+    """Reference voc_clf.py main(): features of VOC07 trainval / test from every checkpoint in turn, the batched SVM evaluation
+    (svm.voc07_svm_eval), Test mAP printed and merged into <checkpoint-dir>/voc07_mAP.txt."""
+    _check_voc_launch(_A)
+    if not torch.cuda.is_available():
+        raise SystemExit("voc_clf: no GPU visible; the kernels run on the MI355X only")
+    from .svm import voc07_svm_eval
+    device = torch.device("cuda", torch.cuda.current_device())
+    _DOWNC = Config(_A.down_config, _A.down_config_override)
+    common_setup(_DOWNC, _A, job_type="downstream")
+    _C = Config(_A.config, list(_A.config_override) + ["AMP", _DOWNC.AMP])       # the encoder's compute dtype follows the downstream config
+    train_dataset = DownstreamDatasetFactory.from_config(_DOWNC, split="trainval")
+    test_dataset = DownstreamDatasetFactory.from_config(_DOWNC, split="test")
+    bs = _DOWNC.OPTIM.BATCH_SIZE
+    loaders = [DataLoader(ds, batch_size=bs, shuffle=False, num_workers=_A.cpu_workers, pin_memory=True, collate_fn=ds.collate_fn)
+               for ds in (train_dataset, test_dataset)]
+    arch = PretrainingModelFactory.from_config(_C).to(device)
+
+    def load(path):
+        CheckpointManager(model=arch).load(path)
+
+    if _A.weight_init == "vlinfo":
+        load(checkpoint_path(_A.checkpoint_dir, _A.start_iter))
+
+    def evaluate():
+        ftr, ttr = extract_features(arch, loaders[0], device)
+        fte, tte = extract_features(arch, loaders[1], device)
+        res = voc07_svm_eval(ftr, ttr.numpy(), fte, tte.numpy())
+        for name, cost, ap in zip(train_dataset.class_names, res["cost"], res["test_ap"]):
+            logger.info(f"SVM {name}: cost {cost}, test AP {ap * 100:.2f}")
+        return res["map"]
+
+    return run_checkpoint_loop(_A.checkpoint_dir, _A.start_iter, _A.freq, evaluate, load)
+
+
+def voc_clf_cli(argv=None):
+    return voc_clf_main(build_voc_clf_parser().parse_args(argv))

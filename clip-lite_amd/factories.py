@@ -54,11 +54,13 @@ class PretrainingDatasetFactory(Factory):
 
 
 class DownstreamDatasetFactory(Factory):
-    """Labelled image sources of the downstream classification evaluation (reference factories.py:534-596, linear_clf.py): DATA.ROOT "random"
-    is the synthetic RandomLabelledDataset; any other root is an image folder root/{train,val}/<class>/<image> (ImageFolderDataset, the
-    layout of the reference's ImageNetDataset / INaturalist2018Dataset). VOC2007 (voc_clf.py: sklearn SVMs) and detection (voc_det.py:
-    detectron2) need libraries that are not available."""
-    PRODUCTS: Dict[str, Callable] = {"random": vdata.RandomLabelledDataset, "folder": vdata.ImageFolderDataset}
+    """Labelled image sources of the downstream evaluations (reference factories.py:534-596, linear_clf.py, voc_clf.py): DATA.ROOT "random"
+    is the synthetic RandomLabelledDataset; a VOC2007 root (the last path component contains "voc") with split "trainval" or "test" is
+    VOC07ClassificationDataset, the source of voc_clf.py's SVM evaluation; any other root is an image folder root/{train,val}/<class>/<image>
+    (ImageFolderDataset, the layout of the reference's ImageNetDataset / INaturalist2018Dataset). A VOC root with another split (linear_clf.py's
+    train / val) and VOC detection (voc_det.py: detectron2) are not supported."""
+    PRODUCTS: Dict[str, Callable] = {"random": vdata.RandomLabelledDataset, "folder": vdata.ImageFolderDataset,
+                                     "voc": vdata.VOC07ClassificationDataset}
     # reference linear_clf.py:105 (the dataset name is the last path component of DATA.ROOT; "imagenet2012" means "imagenet")
     NUM_CLASSES_MAPPING = {"imagenet": 1000, "inaturalist": 8142}
 
@@ -72,8 +74,12 @@ class DownstreamDatasetFactory(Factory):
         _C = config
         root = _C.DATA.ROOT
         if "voc" in cls.dataset_name(root).lower():
-            raise NotImplementedError("VOC2007 classification (reference voc_clf.py) trains sklearn SVMs and detection (voc_det.py) needs detectron2; "
-                                      "neither is available")
+            if split not in ("trainval", "test"):
+                raise NotImplementedError(f"VOC2007 split {split!r}: VOC2007 is evaluated by voc_clf.py's SVMs on 'trainval' / 'test'; "
+                                          "linear_clf.py's train / val splits of VOC and detection (voc_det.py, detectron2) are not supported")
+            transform = tuple(_C.DATA.IMAGE_TRANSFORM_TRAIN if split == "trainval" else _C.DATA.IMAGE_TRANSFORM_VAL)
+            return cls.create("voc", data_root=root, split=split, image_transform=transform, image_size=_C.DATA.IMAGE_CROP_SIZE,
+                              seed=_C.RANDOM_SEED)
         if root == "random":
             return cls.create("random", image_size=_C.DATA.IMAGE_CROP_SIZE, length=50000 if split == "train" else 500, split=split,
                               seed=_C.RANDOM_SEED)

@@ -144,6 +144,12 @@ _SIGNATURES = {
     "clite_infonce_bwd": [_I, _V, _I, _I, _V, _V, _V, _V, _F, _V, _I, _V, _V],
     "clite_xent_fwd": [_V, _I, _I, _I, _V, _I, _V, _V, _V],
     "clite_xent_bwd": [_I, _V, _I, _I, _I, _I, _V, _V, _V, _V, _V, _I, _V],
+    "clite_svm_margin": [_V, _V, _V, _I, _I, _I, _V, _V, _V, _V, _V],
+    "clite_svm_hess_scale": [_V, _V, _U64, _V],
+    "clite_svm_newton_begin": [_V, _I, _I, _I, _V, _V, _V, _V, _F, _I, _F, _V],
+    "clite_svm_cg_update": [_V, _I, _I, _I, _V, _V, _V, _V, _V],
+    "clite_svm_line_search": [_V, _V, _V, _V, _I, _I, _I, _V, _V, _I, _I, _V, _V],
+    "clite_average_precision": [_V, _I, _V, _I, _I, _I, _V, _V],
     "clite_critic_jsd_bwd": [_I, _V, _V, _V, _V, _V, _F, _I, _I, _V, _V, _V, _V, _V, _V],
     "clite_prior_tail_fwd": [_I, _V, _V, _V, _I, _I, _I, _V, _V, _V],
     "clite_prior_tail_bwd": [_I, _V, _V, _V, _V, _F, _I, _I, _V, _V, _V, _V],
@@ -840,6 +846,39 @@ def xent_fwd(logits, ld, B, C, labels, topk, lse, acc):
 
 def xent_bwd(dt, logits, ld, B, Bp, C, lse, labels, acc, gout, dlogits, ldd):
     check(lib().clite_xent_bwd(dt, p(logits), ld, B, Bp, C, p(lse), p(labels), p(acc), p(gout), p(dlogits), ldd, stream_ptr(logits)), "xent_bwd")
+
+
+SVM_STATE = 16                 # include/clite.h CLITE_SVM_STATE: per-problem scalars of the batched SVM solver
+SVM_AP_MAX_ROWS = 8192         # include/clite.h CLITE_SVM_AP_MAX_ROWS
+
+
+def svm_margin(Z, Y, Cw, N, P, ldp, S, H, loss, work):
+    """S = c 1_I (z - y), H = c 1_I, loss[p] = sum c max(0, 1 - y z)^2 over [N][ldp] columns (include/clite.h: clite_svm_margin)."""
+    check(lib().clite_svm_margin(p(Z), p(Y), p(Cw), N, P, ldp, p(S), p(H), p(loss), p(work), stream_ptr(Z)), "svm_margin")
+
+
+def svm_hess_scale(H, Q):
+    check(lib().clite_svm_hess_scale(p(H), p(Q), Q.numel(), stream_ptr(Q)), "svm_hess_scale")
+
+
+def svm_newton_begin(G, ld, Dp, P, X, R, D, state, tol, max_newton, eta_max):
+    check(lib().clite_svm_newton_begin(p(G), ld, Dp, P, p(X), p(R), p(D), p(state), tol, max_newton, eta_max, stream_ptr(G)), "svm_newton_begin")
+
+
+def svm_cg_update(HD, ld, Dp, P, X, R, D, state):
+    check(lib().clite_svm_cg_update(p(HD), ld, Dp, P, p(X), p(R), p(D), p(state), stream_ptr(HD)), "svm_cg_update")
+
+
+def svm_line_search(Z, delta, Y, Cw, N, P, ldp, W, X, ld, Dp, state):
+    check(lib().clite_svm_line_search(p(Z), p(delta), p(Y), p(Cw), N, P, ldp, p(W), p(X), ld, Dp, p(state), stream_ptr(Z)), "svm_line_search")
+
+
+def average_precision(scores, lds, targets, ldt, N, P, ap):
+    """ap[p] = sklearn average_precision_score of column p (targets < 0: ignored); include/clite.h: clite_average_precision."""
+    rc = lib().clite_average_precision(p(scores), lds, p(targets), ldt, N, P, p(ap), stream_ptr(scores))
+    if rc == -2:
+        raise ValueError(f"average_precision: {N} rows exceed the kernel's LDS limit of {SVM_AP_MAX_ROWS}")
+    check(rc, "average_precision")
 
 
 def critic_jsd_bwd(dt, f1, f2, temperature, work, gout, scale, B, D, df1, df2, dtemp, neg=None, neg_inv=None):

@@ -519,6 +519,39 @@ int clite_xent_fwd(const float* logits, int ld, int B, int C, const int64_t* lab
 int clite_xent_bwd(int dtype, const float* logits, int ld, int B, int Bp, int C, const float* lse, const int64_t* labels, const float* acc,
                    const float* gout, void* dlogits, int ldd, void* stream);
 
+/* ---- VOC07 SVM evaluation (reference voc_clf.py:75-121, train_test_single_svm; clip-lite_amd/svm.py). P independent problems
+ *   min_w f_p(w) = 1/2 |w|^2 + sum_i c_ip max(0, 1 - y_ip w.x~_i)^2    (LinearSVC penalty="l2", loss="squared_hinge", intercept_scaling 1)
+ * over one shared f32 matrix X~ [N][Dp] (rows: feature, 1, zeros), solved by batched Newton-CG: every CG iteration is clite_gemm_nt (X~ d^T) and
+ * clite_gemm_tn (2 X~^T (h . q) + d) plus the kernels below. Column arrays (margins Z = X~ W^T, labels Y = +-1, weights Cw = c >= 0, gradient
+ * operand S, Hessian diagonal H) are f32 [N][ldp], ldp % 8 == 0, ldp >= P; row arrays (W, the gradient G, the CG vectors X, R, D, HD) are
+ * f32 [rows >= P][ld], Dp <= ld. Per-problem scalars stay on the device in `state`, f32 [P][CLITE_SVM_STATE], zero-initialised with the
+ * active flag (column 9) set: 0 |grad f(0)|, 1 |grad f(w)|, 2 their ratio, 5 last step length, 6 Newton iterations, 8 CG iterations.
+ * Every sum is formed in one fixed order (no atomics), so results are bitwise reproducible in either deterministic mode. */
+#define CLITE_SVM_STATE 16
+#define CLITE_SVM_AP_MAX_ROWS 8192
+/* S = c 1_I (Z - Y), H = c 1_I with I = {Y Z < 1}; loss (f32 [P]) = sum_i c max(0, 1 - Y Z)^2, the data term of f_p. Columns in [P, ldp) of S and H
+ * are written as zeros. work: f32 [ceil(N / 512)][ldp] scratch. Replaces the per-iteration loss / gradient of LinearSVC.fit (voc_clf.py:100-105). */
+int clite_svm_margin(const float* Z, const float* Y, const float* Cw, int N, int P, int ldp, float* S, float* H, float* loss, float* work, void* stream);
+/* Q *= H elementwise over n floats (n % 4 == 0, 16-byte aligned): the generalised Hessian's diagonal applied to X~ d (voc_clf.py:100-105). */
+int clite_svm_hess_scale(const float* H, float* Q, uint64_t n, void* stream);
+/* One workgroup per problem: |G_p|, the stopping test |G_p| <= tol |grad f_p(0)| or max_newton steps taken (the problem then freezes), and for a
+ * problem that goes on the start of a CG solve of H x = -g: X = 0, R = D = -G, CG tolerance eta |g| with eta = min(eta_max, sqrt(|g| / |g0|)).
+ * G = W + 2 X~^T S (clite_gemm_tn). voc_clf.py:100-105 (LinearSVC.fit). */
+int clite_svm_newton_begin(const float* G, int ld, int Dp, int P, float* X, float* R, float* D, float* state, float tol, int max_newton, float eta_max,
+                           void* stream);
+/* One CG iteration for every problem whose solve is still open: alpha = r.r / d.HD, X += alpha D, R -= alpha HD, then stop when |R| <= the
+ * tolerance or D = R + beta D. Problems that are frozen or done are left untouched. voc_clf.py:100-105 (LinearSVC.fit). */
+int clite_svm_cg_update(const float* HD, int ld, int Dp, int P, float* X, float* R, float* D, float* state, void* stream);
+/* Step length t_p >= 0 minimising f_p(W_p + t X_p) exactly on its piecewise quadratic (safeguarded Newton on f', starting from t = 1), from
+ * Z = X~ W^T and delta = X~ X^T ([N][ldp]); then W_p += t_p X_p. Frozen problems take t = 0. voc_clf.py:100-105 (LinearSVC.fit). */
+int clite_svm_line_search(const float* Z, const float* delta, const float* Y, const float* Cw, int N, int P, int ldp, float* W, const float* X, int ld,
+                          int Dp, float* state, void* stream);
+/* ap[p] (f32 [P]) = sklearn.metrics.average_precision_score(targets[:, p] > 0, scores[:, p]) over the rows with targets[i][p] >= 0 (a negative
+ * target is "ignore"): tied scores form one threshold, AP = sum_n (R_n - R_n-1) P_n; 0 for a column without positives. scores [N][lds], targets
+ * [N][ldt]. One workgroup sorts a column in LDS: N <= CLITE_SVM_AP_MAX_ROWS, else returns -2. Replaces cross_val_score(scoring=
+ * "average_precision") and average_precision_score at voc_clf.py:96-98,121. */
+int clite_average_precision(const float* scores, int lds, const float* targets, int ldt, int N, int P, float* ap, void* stream);
+
 /* ---- Update path (reference train.py:221-226, factories.py:464-482, optim/lookahead.py:88-101) over flat f32 buffers. */
 typedef struct clite_optim_item {   /* one workgroup's slice of one parameter tensor (never straddles tensors) */
   uint64_t start;                   /* element offset into the flat buffers, multiple of 4 */
