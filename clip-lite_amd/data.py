@@ -415,3 +415,80 @@ class VOC07ClassificationDataset(Dataset):
         return {"image": load_image(path, self.image_transform, self.image_size, g), "label": torch.tensor(label, dtype=torch.long)}
 
     collate_fn = staticmethod(_label_collate)
+
+
+# ------------------------------------------------------------------------------------------------ image-text retrieval
+def pre_caption(caption: str, max_words: int = 30) -> str:
+    """The reference's retrieval caption cleanup (data/dataloader.py:1027-1052): lower-case; delete , . ' ! ? " ( ) * # : ; ~; '-' and '/'
+    become spaces; "<person>" becomes "person"; runs of two or more whitespace characters collapse to one space; trailing newlines and
+    surrounding spaces go; at most `max_words` space-separated words are kept. Unlike normalize_caption, accents are kept."""
+    c = re.sub(r"([,.'!?\"()*#:;~])", "", caption.lower()).replace("-", " ").replace("/", " ").replace("<person>", "person")
+    c = re.sub(r"\s{2,}", " ", c).rstrip("\n").strip(" ")
+    words = c.split(" ")
+    if len(words) > max_words:
+        c = " ".join(words[:max_words])
+    return c
+
+
+def _retrieval_collate(items):
+    return {"image": torch.stack([i["image"] for i in items], 0), "index": torch.tensor([i["index"] for i in items], dtype=torch.long)}
+
+
+class RetrievalEvalDataset(Dataset):
+    """Images and captions of an image-text retrieval evaluation, in the reference's two layouts:
+
+    - a JSON list of {"image": path relative to data_root, "caption": [str, ...]} (reference re_eval_dataset, data/dataloader.py:1130-1166:
+      Flickr30k's flickr30k_test.json, ALBEF's COCO Karpathy files) when `ann_file` is given; captions are numbered in file order;
+    - COCO 2017 (reference ReEvalDataset, data/dataloader.py:1055-1127): images data_root/{split}2017/*.jpg, the image id being the integer
+      file stem, captions from data_root/annotations/captions_{split}2017.json grouped by image_id in annotation order. An image without
+      captions stays a row that misses at every k. Deliberate deviation: rows are in sorted file-name order; the reference's glob order
+      is not defined.
+
+    Fields as the reference's: `text` (pre_caption of every caption), `image` (paths, one per row), `img2txt` (row -> caption indices) and
+    `txt2img` (caption index -> row); both maps are keyed by row, and `image_ids` holds the reference's id of every row (the COCO id, or the
+    row itself for the JSON layout). Items: {"image": f32 CHW through load_image(image_transform, image_size), "index": row}."""
+
+    def __init__(self, data_root: str, ann_file: str = "", split: str = "val", image_transform=DEFAULT_IMAGE_TRANSFORM, image_size: int = 224,
+                 max_words: int = 30, seed: int = 0):
+        self.data_root, self.max_words = data_root, max_words
+        self.text, self.image, self.image_ids = [], [], []
+        self.img2txt, self.txt2img = {}, {}
+        if ann_file:
+            with open(ann_file) as f:
+                ann = json.load(f)
+            rows = []
+            for k, a in enumerate(ann):
+                if not isinstance(a.get("caption"), list):
+                    raise ValueError(f"{ann_file}: record {k} has a 'caption' that is not a list (the retrieval layout lists every caption "
+                                     "of an image)")
+                rows.append((k, os.path.join(data_root, a["image"]), a["caption"]))
+        else:
+            image_dir = os.path.join(data_root, f"{split}2017")
+            cap_file = os.path.join(data_root, "annotations", f"captions_{split}2017.json")
+            if not os.path.isdir(image_dir) or not os.path.isfile(cap_file):
+                raise FileNotFoundError(f"COCO 2017 layout not found: need {image_dir}/*.jpg and {cap_file}")
+            with open(cap_file) as f:
+                annotations = json.load(f)["annotations"]
+            by_id = {}
+            for a in annotations:
+                by_id.setdefault(int(a["image_id"]), []).append(a["caption"])
+            names = sorted(n for n in os.listdir(image_dir) if n.endswith(".jpg"))
+            rows = [(int(n[:-4]), os.path.join(image_dir, n), by_id.get(int(n[:-4]), [])) for n in names]
+        for row, (img_id, path, captions) in enumerate(rows):
+            self.image.append(path)
+            self.image_ids.append(img_id)
+            self.img2txt[row] = []
+            for caption in captions:
+                self.img2txt[row].append(len(self.text))
+                self.txt2img[len(self.text)] = row
+                self.text.append(pre_caption(caption, max_words))
+        self.image_transform, self.image_size, self.seed = tuple(image_transform), image_size, seed
+
+    def __len__(self):
+        return len(self.image)
+
+    def __getitem__(self, idx):
+        g = torch.Generator().manual_seed(self.seed * 1000003 + idx)
+        return {"image": load_image(self.image[idx], self.image_transform, self.image_size, g), "index": idx}
+
+    collate_fn = staticmethod(_retrieval_collate)

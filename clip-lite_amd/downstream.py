@@ -1,6 +1,7 @@
 """Command lines of the downstream evaluations: `linear_clf.py` (linear probe / fine-tune, reference linear_clf.py:25-300) and `zero_shot.py`
-(reference zero_shot.py), on ImageClassifier / zero_shot_counts (classify.py). One GPU: the reference's multi-GPU launch, hipGraph capture of the
-classification step, and the `clip` / `imagenet` initialisations (the `clip` package, torchvision downloads) are not available."""
+(reference zero_shot.py), on ImageClassifier / zero_shot_counts (classify.py); `voc_clf.py` (svm.py) and `retrieval.py` (retrieval.py). One
+GPU: the reference's multi-GPU launch, hipGraph capture of the classification step, and the `clip` / `imagenet` initialisations (the `clip`
+package, torchvision downloads) are not available."""
 import argparse
 import os
 
@@ -164,20 +165,24 @@ def build_zero_shot_parser():
     return parser
 
 
-def tokenize_prompts(names, template, max_length, vocab=""):
-    """(input_ids, attention_mask) int64 [C][max_length] of template.format(name) for every class, padded with 0 (padding="max_length",
-    truncation=True, reference zero_shot.py:104-110). The project's WordPiece tokenizer when a vocabulary file is configured."""
+def tokenize_texts(texts, max_length, vocab=""):
+    """(input_ids, attention_mask) int64 [N][max_length] of every text, padded with 0 (padding="max_length", truncation=True: reference
+    zero_shot.py:104-110, retrieval.py:94-100). The project's WordPiece tokenizer when a vocabulary file is configured, else hash_tokenize."""
     from .data import WordPieceTokenizer, hash_tokenize, normalize_caption
     tok = WordPieceTokenizer(vocab) if vocab else None
-    ids = torch.zeros(len(names), max_length, dtype=torch.long)
-    mask = torch.zeros(len(names), max_length, dtype=torch.long)
-    for i, name in enumerate(names):
-        text = template.format(name.replace("_", " "))
+    ids = torch.zeros(len(texts), max_length, dtype=torch.long)
+    mask = torch.zeros(len(texts), max_length, dtype=torch.long)
+    for i, text in enumerate(texts):
         t = tok(normalize_caption(text, max_length), max_length) if tok is not None else hash_tokenize(text, max_length)
         t = list(t)[:max_length]
         ids[i, :len(t)] = torch.tensor(t, dtype=torch.long)
         mask[i, :len(t)] = 1
     return ids, mask
+
+
+def tokenize_prompts(names, template, max_length, vocab=""):
+    """(input_ids, attention_mask) int64 [C][max_length] of template.format(name) for every class (tokenize_texts)."""
+    return tokenize_texts([template.format(name.replace("_", " ")) for name in names], max_length, vocab)
 
 
 def zero_shot_main(_A):
@@ -326,3 +331,63 @@ def voc_clf_main(_A):
 
 def voc_clf_cli(argv=None):
     return voc_clf_main(build_voc_clf_parser().parse_args(argv))
+
+
+# ------------------------------------------------------------------------------------------------ image-text retrieval
+def build_retrieval_parser():
+    parser = common_parser(description="Image-text retrieval (recall@1/5/10 in both directions) of a pretrained model.")
+    parser.set_defaults(num_gpus_per_machine=1)
+    group = parser.add_argument_group("Downstream config arguments.")
+    group.add_argument("--down-config", metavar="FILE", help="Path to a downstream config file.")
+    group.add_argument("--down-config-override", nargs="*", default=[], help="A list of key-value pairs to modify downstream config params.")
+    group = parser.add_argument_group("Checkpointing")
+    group.add_argument("--weight-init", choices=["random", "imagenet", "torchvision", "vlinfo", "clip"], default="vlinfo",
+                       help="'vlinfo': the pretraining checkpoint --checkpoint-path; 'random': the randomly initialised model (the checkpoint is "
+                            "not read). 'imagenet', 'torchvision' (downloads) and 'clip' (the clip package) are not supported.")
+    group.add_argument("--checkpoint-path", required=True, help="Path to load checkpoint and run downstream task evaluation.")
+    group.add_argument("--ann-file", default=None, help="JSON list of {'image', 'caption': [...]} with image paths relative to DATA.ROOT "
+                                                        "(default: by DATA.ROOT, see RetrievalDatasetFactory).")
+    return parser
+
+
+def _check_retrieval_launch(_A):
+    if _A.weight_init == "clip":
+        raise SystemExit("retrieval: --weight-init clip needs the clip package, which is not part of the reference; use vlinfo or random")
+    if _A.weight_init in ("imagenet", "torchvision"):
+        raise SystemExit(f"retrieval: --weight-init {_A.weight_init} needs torchvision model-zoo downloads, which are not supported here; use "
+                         "vlinfo or random")
+    if _A.num_gpus_per_machine > 1 or _A.num_machines > 1:
+        raise SystemExit("retrieval: runs on one GPU (--num-gpus-per-machine 1)")
+    if _A.num_gpus_per_machine == 0:
+        raise SystemExit("retrieval: the encoders and the ranking kernels run on the MI355X only; there is no CPU path (--num-gpus-per-machine 1)")
+
+
+def retrieval_main(_A):
+    """Reference retrieval.py main(): image and text embeddings of the pretraining model in eval mode, the similarity matrix, ranks on the
+    GPU and recall@1/5/10 (retrieval.evaluate). Prints the result dict, then its val_-prefixed form, and returns the dict."""
+    _check_retrieval_launch(_A)
+    if not torch.cuda.is_available():
+        raise SystemExit("retrieval: no GPU visible; the encoders and the ranking kernels run on the MI355X only")
+    from . import retrieval
+    from .factories import RetrievalDatasetFactory
+    device = torch.device("cuda", torch.cuda.current_device())
+    _DOWNC = Config(_A.down_config, _A.down_config_override)
+    common_setup(_DOWNC, _A, job_type="downstream")
+    _C = Config(_A.config, list(_A.config_override) + ["AMP", _DOWNC.AMP])       # the compute dtype follows the downstream config
+    dataset = RetrievalDatasetFactory.from_config(_DOWNC, split="val", ann_file=_A.ann_file)
+    loader = DataLoader(dataset, batch_size=_DOWNC.OPTIM.BATCH_SIZE, shuffle=False, num_workers=_A.cpu_workers, pin_memory=True,
+                        collate_fn=dataset.collate_fn)
+    arch = PretrainingModelFactory.from_config(_C)
+    if _A.weight_init == "vlinfo":
+        CheckpointManager(model=arch).load(_A.checkpoint_path)
+    arch = arch.to(device)
+    ids, mask = tokenize_texts(dataset.text, 30, _C.DATA.TOKENIZER_VOCAB)
+    val_result = retrieval.evaluate(arch, loader, ids, mask)
+    print(val_result)
+    log_stats = {**{f"val_{k}": v for k, v in val_result.items()}}
+    print(log_stats)
+    return val_result
+
+
+def retrieval_cli(argv=None):
+    return retrieval_main(build_retrieval_parser().parse_args(argv))

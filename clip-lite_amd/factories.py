@@ -2,6 +2,7 @@
 :303-434 model factories, :437-487 OptimizerFactory, :490-531 LRSchedulerFactory, :169-238 PretrainingDatasetFactory).
 Model/optimizer/scheduler products are the HIP-backed classes of this package; dataset products are the batch sources of
 data.py (the albumentations / LMDB-backed datasets of the reference need dependencies and files that are not available)."""
+import os
 import re
 from typing import Any, Callable, Dict, Iterable, List
 
@@ -90,6 +91,29 @@ class DownstreamDatasetFactory(Factory):
         if want is not None and ds.num_classes != want:
             raise ValueError(f"{root}/{split} has {ds.num_classes} class directories; {cls.dataset_name(root)} has {want}")
         return ds
+
+
+class RetrievalDatasetFactory(Factory):
+    """Image-text retrieval sources of retrieval.py (reference factories.py:604-616 with ReEvalDataset / re_eval_dataset): an explicit
+    `ann_file` is a JSON list of {"image", "caption": [...]} with image paths relative to DATA.ROOT; otherwise a root whose last path component
+    contains "flickr" reads <root>/data/flickr30k_test.json the same way, and one that contains "coco" is the COCO 2017 layout
+    <root>/{split}2017/*.jpg + <root>/annotations/captions_{split}2017.json. Images go through DATA.IMAGE_TRANSFORM_VAL at IMAGE_CROP_SIZE."""
+    PRODUCTS: Dict[str, Callable] = {"retrieval": vdata.RetrievalEvalDataset}
+
+    @classmethod
+    def from_config(cls, config: Config, split: str = "val", ann_file: str = None):
+        _C = config
+        root = _C.DATA.ROOT
+        name = DownstreamDatasetFactory.dataset_name(root).lower()
+        if not ann_file:
+            if "flickr" in name:
+                ann_file = os.path.join(root, "data", "flickr30k_test.json")
+            elif "coco" not in name:
+                raise ValueError(f"retrieval dataset root {root!r}: supported layouts are a JSON caption list (--ann-file), a Flickr30k root "
+                                 "(last path component contains 'flickr': <root>/data/flickr30k_test.json) and a COCO 2017 root (last path "
+                                 "component contains 'coco': <root>/{split}2017/*.jpg, <root>/annotations/captions_{split}2017.json)")
+        return cls.create("retrieval", data_root=root, ann_file=ann_file or "", split=split,
+                          image_transform=tuple(_C.DATA.IMAGE_TRANSFORM_VAL), image_size=_C.DATA.IMAGE_CROP_SIZE, seed=_C.RANDOM_SEED)
 
 
 class VisualBackboneFactory(Factory):

@@ -150,6 +150,8 @@ _SIGNATURES = {
     "clite_svm_cg_update": [_V, _I, _I, _I, _V, _V, _V, _V, _V],
     "clite_svm_line_search": [_V, _V, _V, _V, _I, _I, _I, _V, _V, _I, _I, _V, _V],
     "clite_average_precision": [_V, _I, _V, _I, _I, _I, _V, _V],
+    "clite_retrieval_rank_i2t": [_V, _I, _I, _I, _V, _V, _V, _V],
+    "clite_retrieval_rank_t2i": [_V, _I, _I, _I, _V, _V, _V, _V],
     "clite_critic_jsd_bwd": [_I, _V, _V, _V, _V, _V, _F, _I, _I, _V, _V, _V, _V, _V, _V],
     "clite_prior_tail_fwd": [_I, _V, _V, _V, _I, _I, _I, _V, _V, _V],
     "clite_prior_tail_bwd": [_I, _V, _V, _V, _V, _F, _I, _I, _V, _V, _V, _V],
@@ -879,6 +881,23 @@ def average_precision(scores, lds, targets, ldt, N, P, ap):
     if rc == -2:
         raise ValueError(f"average_precision: {N} rows exceed the kernel's LDS limit of {SVM_AP_MAX_ROWS}")
     check(rc, "average_precision")
+
+
+def retrieval_rank_i2t(sims, ld, Ni, Nt, cap_off, cap_idx, rank):
+    """rank[i] = rank of image i's best caption in row i of sims [Ni][ld] (columns < Nt); Nt without captions (include/clite.h:
+    clite_retrieval_rank_i2t). cap_off / cap_idx: int32 CSR of the captions, validated by the caller."""
+    check(lib().clite_retrieval_rank_i2t(p(sims), ld, Ni, Nt, p(cap_off), p(cap_idx), p(rank), stream_ptr(sims)), "retrieval_rank_i2t")
+
+
+RETRIEVAL_T2I_ROWS = 128       # include/clite.h CLITE_RETRIEVAL_T2I_ROWS: rows per chunk of the t2i rank kernel
+
+
+def retrieval_rank_t2i(sims, ld, Ni, Nt, txt2img, rank, work):
+    """rank[t] = rank of row txt2img[t] within column t of sims (include/clite.h: clite_retrieval_rank_t2i); txt2img validated by the caller.
+    work: int32 scratch of at least ceil(Ni / RETRIEVAL_T2I_ROWS) * Nt elements."""
+    if work.numel() < (Ni + RETRIEVAL_T2I_ROWS - 1) // RETRIEVAL_T2I_ROWS * Nt:
+        raise ValueError("retrieval_rank_t2i: workspace too small")
+    check(lib().clite_retrieval_rank_t2i(p(sims), ld, Ni, Nt, p(txt2img), p(rank), p(work), stream_ptr(sims)), "retrieval_rank_t2i")
 
 
 def critic_jsd_bwd(dt, f1, f2, temperature, work, gout, scale, B, D, df1, df2, dtemp, neg=None, neg_inv=None):

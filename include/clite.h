@@ -552,6 +552,21 @@ int clite_svm_line_search(const float* Z, const float* delta, const float* Y, co
  * "average_precision") and average_precision_score at voc_clf.py:96-98,121. */
 int clite_average_precision(const float* scores, int lds, const float* targets, int ldt, int N, int P, float* ap, void* stream);
 
+/* ---- Image-text retrieval ranks (reference retrieval.py:150-207, itm_eval; clip-lite_amd/retrieval.py gpu_ranks). sims: f32 [Ni][ld], ld >= Nt,
+ * of which only columns [0, Nt) are read (similarity() pads the text count to a multiple of 8 with zero columns). The rank of an entry is its
+ * 0-based position when its row (i2t) or column (t2i) is sorted by score, highest first, ties to the lower index: np.argsort(-s, kind="stable")
+ * order, 0.0 == -0.0 a tie. Neither direction sorts: each is one counting pass over Ni x Nt x 4 bytes, with integer counts summed in fixed
+ * orders and no atomics (the same result in either deterministic mode). Indices are not checked on the device: the caller validates them. */
+/* rank[i] (int32 [Ni]) = min over the captions c in cap_idx[cap_off[i] .. cap_off[i+1]) of the rank of column c in row i; Nt when image i has
+ * no caption (the reference's 1e20: a miss at every k). That minimum is the rank of the best caption (highest score, lowest index among ties):
+ * one workgroup per row counts the columns that beat it. cap_off: int32 [Ni + 1], cap_idx: int32 [cap_off[Ni]], entries in [0, Nt). */
+int clite_retrieval_rank_i2t(const float* sims, int ld, int Ni, int Nt, const int* cap_off, const int* cap_idx, int* rank, void* stream);
+/* rank[t] (int32 [Nt]) = rank of row txt2img[t] (in [0, Ni)) within column t. Lanes own columns, and the rows are split into chunks of
+ * CLITE_RETRIEVAL_T2I_ROWS over the grid; each chunk's counts go to work (int32 [ceil(Ni / CLITE_RETRIEVAL_T2I_ROWS)][Nt] scratch), and a
+ * second pass adds them in chunk order. */
+#define CLITE_RETRIEVAL_T2I_ROWS 128
+int clite_retrieval_rank_t2i(const float* sims, int ld, int Ni, int Nt, const int* txt2img, int* rank, int* work, void* stream);
+
 /* ---- Update path (reference train.py:221-226, factories.py:464-482, optim/lookahead.py:88-101) over flat f32 buffers. */
 typedef struct clite_optim_item {   /* one workgroup's slice of one parameter tensor (never straddles tensors) */
   uint64_t start;                   /* element offset into the flat buffers, multiple of 4 */
