@@ -298,6 +298,124 @@ class JsonCaptionDataset(_CaptionDataset):
         return c[0] if isinstance(c, list) else c
 
 
+# ------------------------------------------------------------------------------------------------ clustered negative sampling
+_CLUSTER_MAP_RE = re.compile(r"^img_id_cluster_map_(?P<split>[A-Za-z0-9]+)_(?P<k>\d+)\.pkl$")
+
+
+def cluster_map_path(cluster_path: str, split: str, k: int) -> str:
+    """The file scripts/cluster.py writes for one cluster count (reference scripts/cluster.py:146-149)."""
+    return os.path.join(cluster_path, f"img_id_cluster_map_{split}_{k}.pkl")
+
+
+def get_cluster_options(cluster_path: str, split: str):
+    """Cluster counts for which `cluster_path` holds an img_id_cluster_map_<split>_<k>.pkl, ascending (reference data/dataloader.py:
+    get_cluster_options reads them off the file names in os.listdir order, which is undefined; sorted here so that a tie of the schedule goes
+    to the smaller count)."""
+    if not cluster_path or not os.path.isdir(cluster_path):
+        raise FileNotFoundError(f"DATA.CLUSTER_PATH {cluster_path!r} is not a directory; write the cluster maps with cluster.py first")
+    ks = set()
+    for name in os.listdir(cluster_path):
+        m = _CLUSTER_MAP_RE.match(name)
+        if m and m.group("split") == split:
+            ks.add(int(m.group("k")))
+    return sorted(ks)
+
+
+class ClusteredDataset(Dataset):
+    """Pairs with a hard negative from the same caption cluster (reference data/dataloader.py:494-797, the clustered COCO dataset of
+    train.py:150-208) over any `_CaptionDataset`. An item is the base item plus `neg_image` / `neg_input_ids` / `neg_attention_mask`: another
+    record of the item's cluster, put through the same transforms and tokenizer as a positive (it IS `base[neg]`, left / right swap on a flip
+    included). The id of a record is its dataset index, which is what `_CaptionDataset` emits as `image_id` and cluster.py writes as keys.
+
+    The cluster count follows the reference's linear schedule: at iteration `iter_num` (set by `update_iter`, which utils.common.cycle calls at
+    the start of every pass) pred = max(options) * (iter_num - start) / (total - start), and the option closest to pred is used (ties to
+    the smaller); the map is reloaded lazily when the option changes. Draws come from a generator seeded by (seed, index, iter_num):
+    reproducible per index, a new negative each pass.
+
+    Deviation: a cluster with a single member makes the reference draw forever (data/dataloader.py:705-707); here the negative then comes from
+    the whole dataset (never the item itself)."""
+
+    def __init__(self, base, cluster_path: str, split: str = "train", total_iters: int = 500000, negative_sampling_start_iter: int = 0, seed: int = 0):
+        if getattr(base, "mode", None) == "sbert":
+            raise ValueError("ClusteredDataset needs tokenised captions (MODEL.TEXTUAL.NAME train_sbert), not frozen caption encodings")
+        if len(base) < 2:
+            raise ValueError("ClusteredDataset needs at least two records")
+        self.base, self.cluster_path, self.split, self.seed = base, cluster_path, split, int(seed)
+        self.total_iters, self.start_iter = int(total_iters), int(negative_sampling_start_iter)
+        self.cluster_options = get_cluster_options(cluster_path, split)
+        if not self.cluster_options:
+            raise FileNotFoundError(f"no img_id_cluster_map_{split}_<k>.pkl in {cluster_path!r}; write the cluster maps with cluster.py first")
+        self.iter_num = self.start_iter
+        self.num_clusters = None           # the option whose map is loaded
+        self._cluster_of = self._members = None
+        self.update_iter(self.iter_num)
+
+    def scheduled_option(self, iter_num: int) -> int:
+        """The reference's schedule (data/dataloader.py:update_iter): the option closest to max(options) * progress, ties to the smaller."""
+        span = max(self.total_iters - self.start_iter, 1)
+        pred = max(self.cluster_options) * (iter_num - self.start_iter) / span
+        return min(self.cluster_options, key=lambda k: (abs(k - pred), k))
+
+    def update_iter(self, iter_num: int):
+        # Called on the parent process's dataset object. DataLoader workers see it because they are forked anew at every pass (the loaders are
+        # built without persistent_workers; with it the workers would keep the iter_num of their first pass), and each of them loads the map
+        # of a changed option on its first item.
+        self.iter_num = int(iter_num)
+        self._wanted = self.scheduled_option(self.iter_num)
+
+    def _load(self):
+        import pickle
+        path = cluster_map_path(self.cluster_path, self.split, self._wanted)
+        with open(path, "rb") as fh:
+            cmap = pickle.load(fh)
+        outside = [int(i) for i in cmap if not 0 <= int(i) < len(self.base)]
+        if outside:
+            raise ValueError(f"{path} holds {len(outside)} image ids outside the dataset's 0 .. {len(self.base) - 1} (first: {outside[0]}): "
+                             "it was written for another dataset")
+        members = {}
+        for img_id, c in cmap.items():
+            members.setdefault(int(c), []).append(int(img_id))
+        for m in members.values():
+            m.sort()
+        self._cluster_of, self._members, self.num_clusters, self._path = {int(i): int(c) for i, c in cmap.items()}, members, self._wanted, path
+
+    def negative_index(self, idx: int) -> int:
+        if self.num_clusters != self._wanted:          # lazily: DataLoader workers load their own copy after the option changed
+            self._load()
+        if idx not in self._cluster_of:
+            raise KeyError(f"image id {idx} is not in {self._path}")
+        g = torch.Generator().manual_seed((self.seed * 1000003 + idx) * 1000003 + self.iter_num)
+        peers = self._members[self._cluster_of[idx]]
+        if len(peers) > 1:                              # uniform over the cluster's other members
+            j = int(torch.randint(len(peers) - 1, (), generator=g))
+            pos = peers.index(idx) if len(peers) < 64 else _bisect(peers, idx)
+            return peers[j if j < pos else j + 1]
+        j = int(torch.randint(len(self.base) - 1, (), generator=g))
+        return j if j < idx else j + 1
+
+    def __len__(self):
+        return len(self.base)
+
+    def __getitem__(self, idx):
+        idx = int(idx)
+        item = self.base[idx]
+        neg = self.base[self.negative_index(idx)]
+        item["neg_image"], item["neg_caption_tokens"] = neg["image"], neg["caption_tokens"]
+        return item
+
+    def collate_fn(self, items):
+        batch = self.base.collate_fn(items)
+        negs = [{"image_id": i["image_id"], "image": i["neg_image"], "caption_tokens": i["neg_caption_tokens"]} for i in items]
+        nb = self.base.collate_fn(negs)               # the negatives' captions are padded to their own longest row (data/dataloader.py:778-790)
+        batch["neg_image"], batch["neg_input_ids"], batch["neg_attention_mask"] = nb["image"], nb["input_ids"], nb["attention_mask"]
+        return batch
+
+
+def _bisect(sorted_list, x):
+    import bisect
+    return bisect.bisect_left(sorted_list, x)
+
+
 # ------------------------------------------------------------------------------------------------ downstream classification
 IMAGE_EXTENSIONS = (".jpg", ".jpeg", ".png", ".ppm", ".bmp", ".pgm", ".tif", ".tiff", ".webp")     # torchvision datasets.folder
 

@@ -391,3 +391,111 @@ def retrieval_main(_A):
 
 def retrieval_cli(argv=None):
     return retrieval_main(build_retrieval_parser().parse_args(argv))
+
+
+def build_cluster_parser():
+    parser = common_parser(description="Cluster the captions of the pretraining dataset (k-means on the GPU) for clustered negative sampling.")
+    parser.set_defaults(num_gpus_per_machine=1)
+    group = parser.add_argument_group("Clustering (reference scripts/cluster.py:155-176)")
+    group.add_argument("--cluster-root", required=True, help="Directory under which clusters_<max-clusters>/ is written.")
+    group.add_argument("--coco-root", default="", help="Accepted for the reference's command line; image paths come from the dataset records.")
+    group.add_argument("--min-clusters", type=int, default=2)
+    group.add_argument("--max-clusters", type=int, default=10)
+    group.add_argument("--split", type=str, default="train")
+    group.add_argument("--seed", type=int, default=1234, help="Seed of the initial centroids (kmeans.init_rows).")
+    group.add_argument("--encodings", metavar="FILE", default=None, help="A reference-format img_id_encoding_map_<split>.pkl ({id: float vector}): "
+                       "cluster these vectors as they are instead of embedding the captions.")
+    group.add_argument("--batch-size", type=int, default=256, help="Captions per text-encoder batch.")
+    group = parser.add_argument_group("Checkpointing")
+    group.add_argument("--weight-init", choices=["vlinfo", "random"], default="vlinfo",
+                       help="'vlinfo': the text encoder of the pretraining checkpoint --checkpoint-path; 'random': the randomly initialised model.")
+    group.add_argument("--checkpoint-path", default=None, help="Pretraining checkpoint whose text encoder embeds the captions.")
+    return parser
+
+
+@torch.no_grad()
+def embed_captions(model, captions, max_length, vocab="", batch_size=256):
+    """f32 [N][768] on the model's device: the text encoder's features (eval mode, no projection head) of every caption through
+    clite_l2_normalize. Stands in for the reference's paraphrase-mpnet-base-v2 sentence encoder (scripts/cluster.py:115-124), which does not
+    exist offline."""
+    from . import hip
+    rt, enc = model.runtime, model.text_encoder
+    device = next(model.parameters()).device
+    was = enc.training
+    enc.eval()
+    outs = []
+    for i in range(0, len(captions), batch_size):
+        ids, mask = tokenize_texts(captions[i:i + batch_size], max_length, vocab)
+        f = enc({"input_ids": ids.to(device), "attention_mask": mask.to(device)}).contiguous()
+        o = torch.empty_like(f)
+        hip.l2_normalize(rt.dt, f, o, f.shape[0], f.shape[1])
+        outs.append(o.float())
+    enc.train(was)
+    return torch.cat(outs, 0)
+
+
+def _save_pickle(obj, path):
+    import pickle
+    with open(path, "wb") as fh:
+        pickle.dump(obj, fh, protocol=pickle.HIGHEST_PROTOCOL)
+
+
+def cluster_main(_A):
+    """Reference scripts/cluster.py: the first caption of every record of the split embedded once, k-means (kmeans.fit) for every K in
+    [--min-clusters, --max-clusters], and the maps written into <cluster-root>/clusters_<max>/ in the reference's layouts, so that the
+    directory is a valid DATA.CLUSTER_PATH here and for the reference. Returns {K: fit result}."""
+    import pickle
+    import numpy as np
+    from . import kmeans
+    from .factories import PretrainingDatasetFactory
+    from .utils.common import logger
+    if _A.num_gpus_per_machine > 1 or _A.num_machines > 1:
+        raise SystemExit("cluster: runs on one GPU (--num-gpus-per-machine 1)")
+    if _A.num_gpus_per_machine == 0 or not torch.cuda.is_available():
+        raise SystemExit("cluster: the text encoder and the k-means kernels run on the MI355X only; there is no CPU path (--num-gpus-per-machine 1)")
+    if not 2 <= _A.min_clusters <= _A.max_clusters:
+        raise SystemExit("cluster: need 2 <= --min-clusters <= --max-clusters")
+    if _A.encodings is None and _A.weight_init == "vlinfo" and not _A.checkpoint_path:
+        raise SystemExit("cluster: --weight-init vlinfo needs --checkpoint-path (or pass --weight-init random, or --encodings FILE)")
+    device = torch.device("cuda", torch.cuda.current_device())
+    _C = Config(_A.config, _A.config_override)
+    split = str(_A.split)
+    out_dir = os.path.join(_A.cluster_root, f"clusters_{_A.max_clusters}")
+    os.makedirs(out_dir, exist_ok=True)
+    dataset = PretrainingDatasetFactory.from_config(_C, split=split)
+    if dataset.mode == "sbert":
+        raise SystemExit("cluster: needs captions (MODEL.TEXTUAL.NAME train_sbert), not frozen caption encodings")
+    n = len(dataset)
+    captions = [dataset.caption(i) for i in range(n)]
+    if _A.encodings is not None:
+        with open(_A.encodings, "rb") as fh:
+            enc_map = pickle.load(fh)
+        if sorted(int(k) for k in enc_map) != list(range(n)):
+            raise SystemExit(f"cluster: {_A.encodings} must hold one vector for every dataset index 0 .. {n - 1}")
+        X = torch.from_numpy(np.stack([np.asarray(enc_map[i], np.float32) for i in range(n)])).to(device)
+    else:
+        arch = PretrainingModelFactory.from_config(_C)
+        if _A.weight_init == "vlinfo":
+            CheckpointManager(model=arch).load(_A.checkpoint_path)
+        arch = arch.to(device)
+        X = embed_captions(arch, captions, int(_C.DATA.MAX_CAPTION_LENGTH), _C.DATA.TOKENIZER_VOCAB, _A.batch_size)
+    X_host = X.cpu().numpy()
+    _save_pickle({i: [captions[i]] for i in range(n)}, os.path.join(out_dir, f"img_id_caption_map_{split}.pkl"))
+    _save_pickle({i: (dataset.image_path(i) or "") for i in range(n)}, os.path.join(out_dir, f"img_id_filename_map_{split}.pkl"))
+    _save_pickle({i: X_host[i] for i in range(n)}, os.path.join(out_dir, f"img_id_encoding_map_{split}.pkl"))
+    results = {}
+    for K in range(_A.min_clusters, _A.max_clusters + 1):
+        out = kmeans.fit(X, K, niter=200, seed=_A.seed)
+        assign = out["assign"].cpu().tolist()
+        _save_pickle({i: int(assign[i]) for i in range(n)}, os.path.join(out_dir, f"img_id_cluster_map_{split}_{K}.pkl"))
+        counts = out["counts"].cpu()
+        msg = (f"k-means K = {K}: {out['iterations']} iterations, inertia {out['inertia']:.6f}, smallest cluster {int(counts.min())}, "
+               f"largest {int(counts.max())}")
+        logger.info(msg)
+        print(msg)
+        results[K] = out
+    return results
+
+
+def cluster_cli(argv=None):
+    return cluster_main(build_cluster_parser().parse_args(argv))

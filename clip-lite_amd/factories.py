@@ -54,6 +54,22 @@ class PretrainingDatasetFactory(Factory):
         return cls.create(_C.MODEL.NAME, **kwargs)
 
 
+class NegativeSamplingDatasetFactory(Factory):
+    """The clustered dataset of the second training phase (reference factories.py:248-300): the pretraining dataset of the split wrapped
+    in data.ClusteredDataset. Of the reference's kwargs those that apply here: cluster_path, split, total_iters,
+    negative_sampling_start_iter (data_root / tokenizer / transforms are the base dataset's; use_single_caption and coco_root belong to
+    the LMDB reader)."""
+    PRODUCTS: Dict[str, Callable] = {"clusters": vdata.ClusteredDataset}
+
+    @classmethod
+    def from_config(cls, config: Config, split: str = "train"):
+        _C = config
+        kind = "clusters" if "clusters" in _C.DATA.NEGATIVE_SAMPLING else _C.DATA.NEGATIVE_SAMPLING
+        return cls.create(kind, base=PretrainingDatasetFactory.from_config(_C, split=split), cluster_path=_C.DATA.CLUSTER_PATH, split=split,
+                          total_iters=_C.OPTIM.NUM_ITERATIONS, negative_sampling_start_iter=_C.DATA.NEGATIVE_SAMPLING_START_ITERATION,
+                          seed=_C.RANDOM_SEED)
+
+
 class DownstreamDatasetFactory(Factory):
     """Labelled image sources of the downstream evaluations (reference factories.py:534-596, linear_clf.py, voc_clf.py): DATA.ROOT "random"
     is the synthetic RandomLabelledDataset; a VOC2007 root (the last path component contains "voc") with split "trainval" or "test" is

@@ -152,6 +152,10 @@ _SIGNATURES = {
     "clite_average_precision": [_V, _I, _V, _I, _I, _I, _V, _V],
     "clite_retrieval_rank_i2t": [_V, _I, _I, _I, _V, _V, _V, _V],
     "clite_retrieval_rank_t2i": [_V, _I, _I, _I, _V, _V, _V, _V],
+    "clite_kmeans_row_norms": [_V, _I, _I, _I, _F, _V, _V],
+    "clite_kmeans_assign": [_V, _I, _V, _V, _I, _I, _V, _V, _V, _V],
+    "clite_kmeans_accumulate": [_V, _I, _V, _V, _I, _I, _I, _V, _V, _V, _U64, _V],
+    "clite_kmeans_update": [_V, _U64, _V, _I, _I, _I, _V, _I, _V, _V],
     "clite_critic_jsd_bwd": [_I, _V, _V, _V, _V, _V, _F, _I, _I, _V, _V, _V, _V, _V, _V],
     "clite_prior_tail_fwd": [_I, _V, _V, _V, _I, _I, _I, _V, _V, _V],
     "clite_prior_tail_bwd": [_I, _V, _V, _V, _V, _F, _I, _I, _V, _V, _V, _V],
@@ -944,3 +948,36 @@ def adamw_step(pf, gf, mf, v2f, slow, cast, items_ptr, n_items, hp, ss):
 
 def cast_bf16(src, dst, n):
     check(lib().clite_cast_bf16(p(src), p(dst), n, stream_ptr(src)), "cast_bf16")
+
+
+# ------------------------------------------------------------------------------------------------ k-means (clip_lite_amd/kmeans.py)
+KMEANS_MAX_K, KMEANS_BLOCK, KMEANS_CHUNK = 1024, 256, 128       # include/clite.h CLITE_KMEANS_*
+
+
+def kmeans_work_bytes(N, D, K):
+    """include/clite.h CLITE_KMEANS_WORK_BYTES: workspace of kmeans_accumulate / kmeans_update."""
+    a4 = lambda n: (n + 3) // 4 * 4
+    nb = (N + KMEANS_BLOCK - 1) // KMEANS_BLOCK
+    return 4 * (a4(nb * K + 2 * N + 2 * (K + 1)) + a4(nb) + ((N + KMEANS_CHUNK - 1) // KMEANS_CHUNK + K) * D)
+
+
+def kmeans_row_norms(X, ldx, N, D, scale, out):
+    """out[n] = scale |x_n|^2 (include/clite.h: clite_kmeans_row_norms)."""
+    check(lib().clite_kmeans_row_norms(p(X), ldx, N, D, scale, p(out), stream_ptr(X)), "kmeans_row_norms")
+
+
+def kmeans_assign(scores, lds, hc, xnorm, N, K, assign, dist, changed):
+    """assign[n] = argmin_k hc[k] - scores[n][k], ties to the lower k; changed += rows that moved; dist optional (include/clite.h:
+    clite_kmeans_assign)."""
+    check(lib().clite_kmeans_assign(p(scores), lds, p(hc), p(xnorm), N, K, p(assign), p(dist), p(changed), stream_ptr(scores)), "kmeans_assign")
+
+
+def kmeans_accumulate(X, ldx, assign, dist, N, D, K, counts, inertia, work):
+    """Rows grouped by cluster and summed into `work` (uint8, kmeans_work_bytes), counts, inertia (include/clite.h: clite_kmeans_accumulate)."""
+    check(lib().clite_kmeans_accumulate(p(X), ldx, p(assign), p(dist), N, D, K, p(counts), p(inertia), p(work), work.numel() * work.element_size(),
+                                        stream_ptr(X)), "kmeans_accumulate")
+
+
+def kmeans_update(work, counts, N, D, K, Cm, ldc, hc):
+    """C[k] = sum_k / count_k, hc[k] = 0.5 |c_k|^2 from what kmeans_accumulate left (include/clite.h: clite_kmeans_update)."""
+    check(lib().clite_kmeans_update(p(work), work.numel() * work.element_size(), p(counts), N, D, K, p(Cm), ldc, p(hc), stream_ptr(Cm)), "kmeans_update")

@@ -79,6 +79,11 @@ class VLInfoModel(nn.Module):
                 # with hard negatives / augmented views each encoder runs several times per step, so "this module's gradients are final"
                 # only holds after the last backward: the exchange then reduces the whole arena at the end of the step instead
                 ex.defer = extra
+            if rt.device.type == "cuda":
+                # the stream this step is enqueued on: _BertFn.backward orders it behind a text backward that ran elsewhere. Set on every path: a
+                # value left over from an earlier step on another stream (an eager step before a capture) would tie that stream into the capture
+                # as a branch nobody joins, and ending such a capture crashes inside the HIP runtime
+                rt.main_stream = torch.cuda.current_stream(rt.device)
             if extra:
                 return self._forward_with_extras(batch)
             # The two encoders are independent until the loss: the text encoder is enqueued on a second HIP stream so its

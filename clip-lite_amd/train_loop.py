@@ -13,7 +13,7 @@ import torch
 from torch.utils.data import DataLoader, DistributedSampler
 
 from .config import Config
-from .factories import LRSchedulerFactory, OptimizerFactory, PretrainingDatasetFactory, PretrainingModelFactory
+from .factories import LRSchedulerFactory, NegativeSamplingDatasetFactory, OptimizerFactory, PretrainingDatasetFactory, PretrainingModelFactory
 from .utils import distributed as dist
 from .utils.base import Timer, make_directory
 from .utils.checkpointing import CheckpointManager
@@ -37,12 +37,40 @@ def build_parser():
     return parser
 
 
+def check_cluster_assets(_C):
+    """With "clusters" in DATA.NEGATIVE_SAMPLING the cluster maps must exist when the run starts, also when the switch lies in the future: a run
+    must not die at iteration NEGATIVE_SAMPLING_START_ITERATION."""
+    from .data import get_cluster_options
+    path = _C.DATA.CLUSTER_PATH
+    try:
+        options = get_cluster_options(path, "train")
+    except FileNotFoundError:
+        options = []
+    if not options:
+        raise FileNotFoundError(f"DATA.NEGATIVE_SAMPLING {_C.DATA.NEGATIVE_SAMPLING!r} needs img_id_cluster_map_train_<k>.pkl files in DATA.CLUSTER_PATH "
+                                f"({path!r}), and there are none: write them with cluster.py (python cluster.py --config ... --cluster-root ...)")
+    return options
+
+
 def init_dataloaders(_C, _A, type="normal"):
-    if type != "normal":
-        raise NotImplementedError("clustered negative sampling (reference train.py:70-76) needs the faiss/LMDB assets and is out of scope")
-    train_dataset = PretrainingDatasetFactory.from_config(_C, split="train")
-    val_dataset = PretrainingDatasetFactory.from_config(_C, split="val")
-    batch_size = _C.OPTIM.BATCH_SIZE // dist.get_world_size()
+    """reference train.py:60-118. type "clusters": the clustered datasets at half the per-rank batch (train.py:75: the step then encodes B / 2
+    pairs and B / 2 negatives)."""
+    if type == "normal":
+        train_dataset = PretrainingDatasetFactory.from_config(_C, split="train")
+        val_dataset = PretrainingDatasetFactory.from_config(_C, split="val")
+        batch_size = _C.OPTIM.BATCH_SIZE // dist.get_world_size()
+    elif type == "clusters":
+        from .data import get_cluster_options
+        check_cluster_assets(_C)
+        train_dataset = NegativeSamplingDatasetFactory.from_config(_C, split="train")
+        if get_cluster_options(_C.DATA.CLUSTER_PATH, "val"):
+            val_dataset = NegativeSamplingDatasetFactory.from_config(_C, split="val")
+        else:
+            logger.warning(f"no img_id_cluster_map_val_<k>.pkl in {_C.DATA.CLUSTER_PATH!r}: validating on the normal val dataset (no negatives)")
+            val_dataset = PretrainingDatasetFactory.from_config(_C, split="val")
+        batch_size = (_C.OPTIM.BATCH_SIZE // dist.get_world_size()) // 2
+    else:
+        raise KeyError(f"init_dataloaders: unknown type {type!r} (normal | clusters)")
     distributed = dist.get_world_size() > 1
     train_sampler = DistributedSampler(train_dataset, shuffle=True) if distributed else None
     val_sampler = DistributedSampler(val_dataset, shuffle=False) if distributed else None
@@ -110,6 +138,17 @@ class TrainStep:
         main.wait_stream(side)
         self._pending_rest = False
         self._rest_ev = None
+
+    def recapture(self):
+        """Forget the captured step: complete a deferred update, drop the graphs and their static buffers, and let the next calls warm up and
+        capture again on the batches that arrive then. train_loop.main calls it when the loader switches to clustered negative sampling: those
+        batches (new neg_* keys, half the rows) do not fit the captured graphs, and every later step would silently take the eager path."""
+        self.finish()
+        torch.cuda.synchronize()
+        self._g = self._g_update = self._graphs = None
+        self._static_batch = self._static_out = None
+        self._keep = self._staged = None
+        self._eager_steps = 0
 
     def _eager(self, batch):
         # (another TrainStep on the same model may hold the pending share: Arena.flush_pending reaches whichever one registered last — ADVICE r4)
@@ -644,8 +683,15 @@ def main(_A: argparse.Namespace):
     else:
         start_iteration = 0
 
-    train_dataloader, val_dataloader = init_dataloaders(_C, _A, type="normal")
-    train_dataloader_iter = cycle(train_dataloader, device, start_iteration, type="normal")
+    # reference train.py:150-172: a run resumed at or after the switch starts on the clustered loaders
+    clusters = "clusters" in _C.DATA.NEGATIVE_SAMPLING
+    if clusters:
+        check_cluster_assets(_C)
+    loader_type = "clusters" if clusters and start_iteration >= _C.DATA.NEGATIVE_SAMPLING_START_ITERATION else "normal"
+    if loader_type == "clusters":
+        logger.info("Starting clustered negative sampling, loading new dataloaders...")
+    train_dataloader, val_dataloader = init_dataloaders(_C, _A, type=loader_type)
+    train_dataloader_iter = cycle(train_dataloader, device, start_iteration, type=loader_type)
 
     exchange = None
     if dist.get_world_size() > 1:
@@ -660,6 +706,12 @@ def main(_A: argparse.Namespace):
     step = TrainStep(model, optimizer, scheduler, scaler, _C.OPTIM.CLIP_GRAD_NORM, exchange, graph=not _A.no_hip_graph,
                      pad_to=min(int(_C.DATA.MAX_CAPTION_LENGTH), 32), allow_eager_fallback=_A.allow_eager_fallback, defer_update=True)
     for iteration in range(start_iteration + 1, _C.OPTIM.NUM_ITERATIONS + 1):
+        if clusters and iteration == _C.DATA.NEGATIVE_SAMPLING_START_ITERATION and loader_type == "normal":      # reference train.py:190-203
+            logger.info("Starting clustered negative sampling, loading new dataloaders...")
+            loader_type = "clusters"
+            train_dataloader, val_dataloader = init_dataloaders(_C, _A, type="clusters")
+            train_dataloader_iter = cycle(train_dataloader, device, iteration, type="clusters")
+            step.recapture()           # the clustered batches do not fit the captured step: warm up and capture again on them
         timer.tic()
         batch = next(train_dataloader_iter)
         output_dict = step(batch)

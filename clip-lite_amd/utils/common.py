@@ -58,8 +58,8 @@ def cycle(dataloader, device, start_iteration: int = 0, type: str = "normal", pr
         if isinstance(sampler, torch.utils.data.DistributedSampler):
             logger.info(f"Beginning new epoch, setting shuffle seed {loaded}")
             sampler.set_epoch(loaded)
-            if type == "clusters":
-                sampler.dataset.update_iter(loaded)
+        if type == "clusters":            # every pass, with or without a DistributedSampler (the reference only ever runs with one)
+            dataloader.dataset.update_iter(loaded)
         for batch in dataloader:
             pending.append(stager.stage(batch))
             loaded += 1

@@ -567,6 +567,44 @@ int clite_retrieval_rank_i2t(const float* sims, int ld, int Ni, int Nt, const in
 #define CLITE_RETRIEVAL_T2I_ROWS 128
 int clite_retrieval_rank_t2i(const float* sims, int ld, int Ni, int Nt, const int* txt2img, int* rank, int* work, void* stream);
 
+/* ---- k-means of caption embeddings for clustered negative sampling (reference scripts/cluster.py:131-140: faiss.Kmeans(d, k, niter=200).train, then
+ * index.search(x, 1); clip-lite_amd/kmeans.py). Lloyd's algorithm on f32 points X [N][ldx] (D % 8 == 0, ldx >= D), 2 <= K <= CLITE_KMEANS_MAX_K,
+ * N >= K. One iteration: scores = X C^T by clite_gemm_nt with dtype CLITE_F32 (K padded to a multiple of 8), clite_kmeans_assign,
+ * clite_kmeans_accumulate, clite_kmeans_update. No float atomics: every sum is formed in an order that depends on the assignment alone, so the
+ * centroids are bitwise reproducible from run to run and identical in both settings of clite_set_deterministic. A 16-byte aligned X with
+ * ldx % 4 == 0 is read with 16-byte loads, any other through a scalar path. Every entry returns -1 for a null pointer or a shape outside the
+ * above, -2 for a workspace that is too small; clite_kmeans_accumulate returns -3 when it cannot enqueue the zero fill of its histogram. */
+#define CLITE_KMEANS_MAX_K 1024
+#define CLITE_KMEANS_BLOCK 256   /* rows per block of the counting sort that groups the rows by cluster */
+#define CLITE_KMEANS_CHUNK 128   /* rows per partial sum: a cluster of n rows is summed as ceil(n / 128) partial rows, added in order */
+/* Workspace of clite_kmeans_accumulate / _update in bytes (16-byte aligned base): with nb = ceil(N / 256), int32 hist [nb][K], rank [N],
+ * order [N], start [K + 1], chunk start [K + 1]; f32 distance partials [nb]; f32 partial sums [ceil(N / 128) + K][D]; the int32 and the [nb]
+ * parts each rounded up to 4 elements. 8 840 128 bytes (8.43 MiB) at N = 118 287, D = 768, K = 1024. */
+#define CLITE_KMEANS_ALIGN4(n) (((uint64_t)(n) + 3) & ~(uint64_t)3)
+#define CLITE_KMEANS_WORK_BYTES(N, D, K)                                                                                                        \
+  (4 * (CLITE_KMEANS_ALIGN4((((uint64_t)(N) + CLITE_KMEANS_BLOCK - 1) / CLITE_KMEANS_BLOCK) * (uint64_t)(K) + 2 * (uint64_t)(N) +               \
+                            2 * ((uint64_t)(K) + 1)) +                                                                                          \
+        CLITE_KMEANS_ALIGN4(((uint64_t)(N) + CLITE_KMEANS_BLOCK - 1) / CLITE_KMEANS_BLOCK) +                                                    \
+        (((uint64_t)(N) + CLITE_KMEANS_CHUNK - 1) / CLITE_KMEANS_CHUNK + (uint64_t)(K)) * (uint64_t)(D)))
+/* out[n] (f32 [N]) = scale * |x_n|^2: the row term of the squared distances (scale 1), and 0.5 |c_k|^2 of the initial centroids (scale 0.5).
+ * cluster.py:136-139 (the norms faiss's IndexFlatL2 keeps). */
+int clite_kmeans_row_norms(const float* X, int ldx, int N, int D, float scale, float* out, void* stream);
+/* assign[n] (int32 [N]) = argmin over k < K of hc[k] - scores[n][k], hc[k] = 0.5 |c_k|^2, ties to the lower k (0.0 == -0.0 is a tie); columns in
+ * [K, lds) are never compared. A NaN value never wins: the row takes the lowest k whose value is not a NaN, or 0 when every value is one.
+ * *changed (int32, device) += the number of rows whose previous assign[n] differs (integer atomic). dist (f32 [N], optional, needs xnorm =
+ * |x_n|^2) = max(0, |x_n|^2 - 2 x_n.c + |c|^2) for the chosen centroid, 0 for an all-NaN row. cluster.py:139-140 (the assignment inside train, and index.search(x, 1)). */
+int clite_kmeans_assign(const float* scores, int lds, const float* hc, const float* xnorm, int N, int K, int* assign, float* dist, int* changed,
+                        void* stream);
+/* Groups the rows by cluster (stable: ascending row index inside a cluster) and leaves in `work` the partial sums of every cluster's rows, read
+ * once from X; counts[k] (int32 [K]) = rows assigned to k; *inertia (double, device, optional) = sum of dist (optional f32 [N]) in a fixed
+ * order. A row whose assign[n] is outside [0, K) joins no cluster. cluster.py:136-139 (the centroid update inside faiss.Kmeans.train). */
+int clite_kmeans_accumulate(const float* X, int ldx, const int* assign, const float* dist, int N, int D, int K, int* counts, double* inertia,
+                            void* work, uint64_t work_bytes, void* stream);
+/* From the `work` and counts that clite_kmeans_accumulate left for the same (N, D, K): C[k] (f32 [K][ldc], 16-byte aligned, ldc % 4 == 0) =
+ * sum_k / count_k and hc[k] = 0.5 |c_k|^2; an empty cluster keeps its centroid (the driver relocates before it gets here).
+ * cluster.py:136-139. */
+int clite_kmeans_update(const void* work, uint64_t work_bytes, const int* counts, int N, int D, int K, float* C, int ldc, float* hc, void* stream);
+
 /* ---- Update path (reference train.py:221-226, factories.py:464-482, optim/lookahead.py:88-101) over flat f32 buffers. */
 typedef struct clite_optim_item {   /* one workgroup's slice of one parameter tensor (never straddles tensors) */
   uint64_t start;                   /* element offset into the flat buffers, multiple of 4 */
