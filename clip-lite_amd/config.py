@@ -109,6 +109,10 @@ class Config(object):
         _C.DATA.USE_PERCENTAGE = 100.0
         _C.DATA.IMAGE_TRANSFORM_TRAIN = ["random_resized_crop", "horizontal_flip", "color_jitter", "normalize"]
         _C.DATA.IMAGE_TRANSFORM_VAL = ["smallest_resize", "center_crop", "normalize"]
+        # (not reference keys) augment on the GPU: loader workers only decode and pre-size each image to a uint8 canvas whose shorter side is
+        # GPU_AUGMENT_SOURCE_SIZE (or the configured smallest_resize); crop, resample, flip, colour jitter and normalisation run as HIP kernels (augment.py)
+        _C.DATA.GPU_AUGMENT = False
+        _C.DATA.GPU_AUGMENT_SOURCE_SIZE = 256
         _C.DATA.JSON_FILES_TRAIN = [
             "/export/share/junnan-li/ALBEF/data/coco_karpathy_train.json",
             "/export/share/junnan-li/ALBEF/data/vg_caption.json",

@@ -214,11 +214,24 @@ def load_image(path: str, transforms, crop_size: int, generator=None, return_fli
 
 
 class _CaptionDataset(Dataset):
+    """Image-caption pairs. gpu_augment: items carry a uint8 canvas and a plan row instead of the finished image (augment.py; the kernels finish it
+    on the device), source_size being DATA.GPU_AUGMENT_SOURCE_SIZE. visual_self_supervised: a second view of the image - `aug_image`, a second
+    load_image of the same file from the same generator, or with gpu_augment `aug_image_plan`, a second plan row over the same canvas.
+    textual_self_supervised: `aug_input_ids` / `aug_attention_mask` from another caption of the same record (reference data/dataloader.py:335-339,
+    390-407); a record with a single distinct caption re-uses it (the reference's `while aug_caption == caption` loops for ever there)."""
+
     def __init__(self, mode: str, image_size: int, max_caption_length: int, length: int, seed: int = 0, tokenizer_vocab: str = "",
-                 image_transform=DEFAULT_IMAGE_TRANSFORM):
+                 image_transform=DEFAULT_IMAGE_TRANSFORM, gpu_augment: bool = False, source_size: int = 256, visual_self_supervised: bool = False,
+                 textual_self_supervised: bool = False):
         self.mode, self.image_size, self.max_len, self.length, self.seed = mode, image_size, max_caption_length, length, seed
         self.tokenizer = WordPieceTokenizer(tokenizer_vocab) if tokenizer_vocab else None
         self.image_transform = tuple(image_transform)
+        self.gpu_augment, self.visual_ssl, self.textual_ssl = bool(gpu_augment), bool(visual_self_supervised), bool(textual_self_supervised)
+        self.textual_ssl = self.textual_ssl and mode != "sbert"          # (frozen caption encodings: there is no caption to re-tokenise)
+        if self.gpu_augment:
+            from . import augment
+            self.canvas_side = augment.canvas_short_side(self.image_transform, image_size, source_size)
+            self.canvas_cap = augment.canvas_capacity(self.canvas_side)
 
     def tokenize(self, caption: str):
         if self.tokenizer is not None:            # the reference's order: NormalizeCaption, then the BERT tokenizer (data/dataloader.py:194-202)
@@ -234,58 +247,113 @@ class _CaptionDataset(Dataset):
     def caption(self, idx):
         raise NotImplementedError
 
+    def captions(self, idx):
+        """Every caption of the record; `caption(idx)` is the one the pair uses."""
+        return [self.caption(idx)]
+
+    def aug_caption(self, idx, caption, generator):
+        """Another caption of the record, uniform over those that differ from `caption`; `caption` itself when there is none."""
+        others = [c for c in self.captions(idx) if c != caption]
+        if not others:
+            return caption
+        return others[int(torch.randint(len(others), (), generator=generator))]
+
+    def _gpu_item(self, path, g):
+        """canvas + plan row(s) of one record (augment.py); returns (item entries, flipped)"""
+        from . import augment
+        if path is not None and os.path.isfile(path):
+            from PIL import Image
+            canvas = augment.make_canvas(Image.open(path), self.canvas_side)
+        else:
+            canvas = augment.synthetic_canvas(self.canvas_side, g)
+        h, w = canvas.shape[:2]
+        plan = augment.plan_transforms(h, w, self.image_transform, self.image_size, g)
+        out = {"image_u8": torch.from_numpy(canvas), "image_plan": plan}
+        if self.visual_ssl:
+            out["aug_image_plan"] = augment.plan_transforms(h, w, self.image_transform, self.image_size, g)
+        return out, bool(plan[augment.PLAN_FLIP] != 0)
+
     def __getitem__(self, idx):
         g = torch.Generator().manual_seed(self.seed * 1000003 + idx)
         path = self.image_path(idx)
         flipped = False
-        if path is not None and os.path.isfile(path):
-            image, flipped = load_image(path, self.image_transform, self.image_size, g, return_flipped=True)
+        item = {"image_id": torch.tensor(idx, dtype=torch.long)}
+        if self.gpu_augment:
+            views, flipped = self._gpu_item(path, g)
+            item.update(views)
+        elif path is not None and os.path.isfile(path):
+            item["image"], flipped = load_image(path, self.image_transform, self.image_size, g, return_flipped=True)
+            if self.visual_ssl:
+                item["aug_image"] = load_image(path, self.image_transform, self.image_size, g)
         else:
-            image = torch.randn(3, self.image_size, self.image_size, generator=g)
-        item = {"image_id": torch.tensor(idx, dtype=torch.long), "image": image}
+            item["image"] = torch.randn(3, self.image_size, self.image_size, generator=g)
+            if self.visual_ssl:
+                item["aug_image"] = torch.randn(3, self.image_size, self.image_size, generator=g)
         if self.mode == "sbert":
             item["caption_encodings"] = torch.randn(768, generator=g)
         else:
             caption = self.caption(idx)
+            aug = self.aug_caption(idx, caption, g) if self.textual_ssl else None
             if flipped:          # the image transforms run on (image, RAW caption) pairs in the reference: a flipped image swaps left / right
                 caption = swap_left_right(caption)
             item["caption_tokens"] = torch.tensor(self.tokenize(caption), dtype=torch.long)
+            if aug is not None:
+                item["aug_caption_tokens"] = torch.tensor(self.tokenize(aug), dtype=torch.long)
         return item
 
+    @staticmethod
+    def _pad_captions(tokens):
+        L = max(len(t) for t in tokens)
+        ids = torch.zeros(len(tokens), L, dtype=torch.long)             # pad_token_id = 0
+        mask = torch.zeros(len(tokens), L, dtype=torch.long)
+        for r, t in enumerate(tokens):
+            ids[r, :len(t)] = t
+            mask[r, :len(t)] = 1
+        return ids, mask
+
     def collate_fn(self, items):
-        batch = {"image_id": torch.stack([i["image_id"] for i in items]), "image": torch.stack([i["image"] for i in items])}
+        batch = {"image_id": torch.stack([i["image_id"] for i in items])}
+        if "image_u8" in items[0]:          # fixed-capacity tensors: every batch has the same shapes
+            from . import augment
+            batch["image_u8"], batch["image_hw"] = augment.pack_canvases([i["image_u8"] for i in items], self.canvas_cap)
+            for k in ("image_plan", "aug_image_plan"):
+                if k in items[0]:
+                    batch[k] = torch.stack([i[k] for i in items])
+                    augment.check_plan(batch[k], batch["image_hw"], self.image_size)
+        else:
+            batch["image"] = torch.stack([i["image"] for i in items])
+            if "aug_image" in items[0]:
+                batch["aug_image"] = torch.stack([i["aug_image"] for i in items])
         if self.mode == "sbert":
             batch["caption_encodings"] = torch.stack([i["caption_encodings"] for i in items])
         else:
-            L = max(len(i["caption_tokens"]) for i in items)
-            ids = torch.zeros(len(items), L, dtype=torch.long)             # pad_token_id = 0
-            mask = torch.zeros(len(items), L, dtype=torch.long)
-            for r, i in enumerate(items):
-                n = len(i["caption_tokens"])
-                ids[r, :n] = i["caption_tokens"]
-                mask[r, :n] = 1
-            batch["input_ids"], batch["attention_mask"] = ids, mask
+            batch["input_ids"], batch["attention_mask"] = self._pad_captions([i["caption_tokens"] for i in items])
+            if "aug_caption_tokens" in items[0]:
+                batch["aug_input_ids"], batch["aug_attention_mask"] = self._pad_captions([i["aug_caption_tokens"] for i in items])
         return batch
 
 
 class RandomDataset(_CaptionDataset):
     def __init__(self, mode="train_sbert", image_size=224, max_caption_length=30, length=118000, seed=0, tokenizer_vocab="",
-                 image_transform=DEFAULT_IMAGE_TRANSFORM):
-        super().__init__(mode, image_size, max_caption_length, length, seed, tokenizer_vocab, image_transform)
+                 image_transform=DEFAULT_IMAGE_TRANSFORM, **augment_kwargs):
+        super().__init__(mode, image_size, max_caption_length, length, seed, tokenizer_vocab, image_transform, **augment_kwargs)
 
     def caption(self, idx):
         return CAPTIONS[idx % len(CAPTIONS)]
 
+    def aug_caption(self, idx, caption, generator):          # the next of the fixed captions (no draw)
+        return CAPTIONS[(idx + 1) % len(CAPTIONS)]
+
 
 class JsonCaptionDataset(_CaptionDataset):
     def __init__(self, json_files, mode="train_sbert", image_size=224, max_caption_length=30, seed=0, tokenizer_vocab="",
-                 image_transform=DEFAULT_IMAGE_TRANSFORM, data_root=""):
+                 image_transform=DEFAULT_IMAGE_TRANSFORM, data_root="", **augment_kwargs):
         self.records = []
         for f in json_files:
             with open(f) as fh:
                 self.records += json.load(fh)
         self.data_root = data_root
-        super().__init__(mode, image_size, max_caption_length, len(self.records), seed, tokenizer_vocab, image_transform)
+        super().__init__(mode, image_size, max_caption_length, len(self.records), seed, tokenizer_vocab, image_transform, **augment_kwargs)
 
     def image_path(self, idx):
         path = self.records[idx].get("image")
@@ -296,6 +364,10 @@ class JsonCaptionDataset(_CaptionDataset):
     def caption(self, idx):
         c = self.records[idx]["caption"]
         return c[0] if isinstance(c, list) else c
+
+    def captions(self, idx):
+        c = self.records[idx]["caption"]
+        return list(c) if isinstance(c, list) else [c]
 
 
 # ------------------------------------------------------------------------------------------------ clustered negative sampling
@@ -400,14 +472,18 @@ class ClusteredDataset(Dataset):
         idx = int(idx)
         item = self.base[idx]
         neg = self.base[self.negative_index(idx)]
-        item["neg_image"], item["neg_caption_tokens"] = neg["image"], neg["caption_tokens"]
+        for k in ("image", "image_u8", "image_plan", "caption_tokens"):          # (a GPU-augmenting base: the negative's canvas and plan row)
+            if k in neg:
+                item["neg_" + k] = neg[k]
         return item
 
     def collate_fn(self, items):
         batch = self.base.collate_fn(items)
-        negs = [{"image_id": i["image_id"], "image": i["neg_image"], "caption_tokens": i["neg_caption_tokens"]} for i in items]
+        negs = [{"image_id": i["image_id"], **{k[4:]: v for k, v in i.items() if k.startswith("neg_")}} for i in items]
         nb = self.base.collate_fn(negs)               # the negatives' captions are padded to their own longest row (data/dataloader.py:778-790)
-        batch["neg_image"], batch["neg_input_ids"], batch["neg_attention_mask"] = nb["image"], nb["input_ids"], nb["attention_mask"]
+        for k in ("image", "image_u8", "image_hw", "image_plan", "input_ids", "attention_mask"):
+            if k in nb:
+                batch["neg_" + k] = nb[k]
         return batch
 
 

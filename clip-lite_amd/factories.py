@@ -42,7 +42,9 @@ class PretrainingDatasetFactory(Factory):
         kwargs = {"mode": _C.MODEL.TEXTUAL.NAME, "image_size": _C.DATA.IMAGE_CROP_SIZE, "max_caption_length": _C.DATA.MAX_CAPTION_LENGTH,
                   "tokenizer_vocab": _C.DATA.TOKENIZER_VOCAB,
                   # transform names as configured; resize / crop transforms take IMAGE_CROP_SIZE (reference factories.py:213-224)
-                  "image_transform": tuple(getattr(_C.DATA, f"IMAGE_TRANSFORM_{split.upper()}"))}
+                  "image_transform": tuple(getattr(_C.DATA, f"IMAGE_TRANSFORM_{split.upper()}")),
+                  "gpu_augment": _C.DATA.GPU_AUGMENT, "source_size": _C.DATA.GPU_AUGMENT_SOURCE_SIZE,
+                  "visual_self_supervised": _C.MODEL.VISUAL.SELF_SUPERVISED, "textual_self_supervised": _C.MODEL.TEXTUAL.SELF_SUPERVISED}
         if _C.MODEL.NAME == "json":
             kwargs["json_files"] = list(_C.DATA.JSON_FILES_TRAIN if split == "train" else _C.DATA.JSON_FILES_VAL)
             kwargs["data_root"] = _C.DATA.ROOT

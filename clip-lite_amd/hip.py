@@ -156,6 +156,8 @@ _SIGNATURES = {
     "clite_kmeans_assign": [_V, _I, _V, _V, _I, _I, _V, _V, _V, _V],
     "clite_kmeans_accumulate": [_V, _I, _V, _V, _I, _I, _I, _V, _V, _V, _U64, _V],
     "clite_kmeans_update": [_V, _U64, _V, _I, _I, _I, _V, _I, _V, _V],
+    "clite_augment_gray_mean": [_V, _V, C.c_int64, _V, _I, _I, _V, _V, _V, _V, _V],
+    "clite_augment_apply": [_I, _I, _V, _V, C.c_int64, _V, _V, _I, _I, _V, _I, _I, _I, _V, _V, _V],
     "clite_critic_jsd_bwd": [_I, _V, _V, _V, _V, _V, _F, _I, _I, _V, _V, _V, _V, _V, _V],
     "clite_prior_tail_fwd": [_I, _V, _V, _V, _I, _I, _I, _V, _V, _V],
     "clite_prior_tail_bwd": [_I, _V, _V, _V, _V, _F, _I, _I, _V, _V, _V, _V],
@@ -981,3 +983,53 @@ def kmeans_accumulate(X, ldx, assign, dist, N, D, K, counts, inertia, work):
 def kmeans_update(work, counts, N, D, K, Cm, ldc, hc):
     """C[k] = sum_k / count_k, hc[k] = 0.5 |c_k|^2 from what kmeans_accumulate left (include/clite.h: clite_kmeans_update)."""
     check(lib().clite_kmeans_update(p(work), work.numel() * work.element_size(), p(counts), N, D, K, p(Cm), ldc, p(hc), stream_ptr(Cm)), "kmeans_update")
+
+
+# ------------------------------------------------------------------------------------------------ image augmentation (clip_lite_amd/augment.py)
+AUGMENT_PLAN_W, AUGMENT_MAX_SCALE = 16, 4
+AUGMENT_NCHW, AUGMENT_NHWC4 = 0, 1
+
+
+def augment_gray_blocks(S):
+    """include/clite.h CLITE_AUGMENT_GRAY_BLOCKS: partial sums per view of augment_gray_mean."""
+    return (S * S + 255) // 256
+
+
+def _host_ptr(t, dtype, shape):
+    """Pointer of an optional host mirror (a contiguous CPU tensor that outlives the call: validated before the launch, never read later)."""
+    if t is None:
+        return None
+    if t.is_cuda or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError("augment: a host mirror must be a contiguous CPU tensor of the table's dtype and shape")
+    return t.data_ptr()
+
+
+def _augment_tables(canvases, hw, plan):
+    N = canvases.shape[0]
+    if canvases.dtype != torch.uint8 or canvases.dim() != 2 or not canvases.is_contiguous():
+        raise ValueError("augment: canvases must be a contiguous uint8 [N][cap] tensor")
+    if hw.dtype != torch.int32 or tuple(hw.shape) != (N, 2) or not hw.is_contiguous():
+        raise ValueError("augment: hw must be a contiguous int32 [N][2] tensor")
+    if plan.dtype != torch.float32 or tuple(plan.shape) != (N, AUGMENT_PLAN_W) or not plan.is_contiguous():
+        raise ValueError(f"augment: plan must be a contiguous f32 [N][{AUGMENT_PLAN_W}] tensor")
+    return N, canvases.shape[1]
+
+
+def augment_gray_mean(canvases, hw, plan, S, mean, work, plan_host=None, hw_host=None):
+    """mean[n] = the view's mean gray in front of its contrast op (include/clite.h: clite_augment_gray_mean)."""
+    N, cap = _augment_tables(canvases, hw, plan)
+    if mean.dtype != torch.float32 or mean.numel() < N or work.dtype != torch.float32 or work.numel() < N * augment_gray_blocks(S):
+        raise ValueError("augment_gray_mean: mean / workspace too small")
+    check(lib().clite_augment_gray_mean(p(canvases), p(hw), cap, p(plan), N, S, p(mean), p(work), _host_ptr(plan_host, torch.float32, plan.shape),
+                                        _host_ptr(hw_host, torch.int32, hw.shape), stream_ptr(canvases)), "augment_gray_mean")
+
+
+def augment_apply(form, dt, canvases, hw, plan, mean, S, out, pad=0, Hp=0, Wp=0, plan_host=None, hw_host=None):
+    """The views of `plan` as f32 NCHW (form AUGMENT_NCHW) or in the stem's padded NHWC4 form (include/clite.h: clite_augment_apply)."""
+    N, cap = _augment_tables(canvases, hw, plan)
+    want = (N, 3, S, S) if form == AUGMENT_NCHW else (N, Hp, Wp, 4)
+    if tuple(out.shape) != want or out.dtype != TORCH_DTYPE[dt] or not out.is_contiguous() or mean.dtype != torch.float32 or mean.numel() < N:
+        raise ValueError(f"augment_apply: out must be a contiguous {TORCH_DTYPE[dt]} tensor of shape {want}")
+    check(lib().clite_augment_apply(form, dt, p(canvases), p(hw), cap, p(plan), p(mean), N, S, p(out), pad, Hp, Wp,
+                                    _host_ptr(plan_host, torch.float32, plan.shape), _host_ptr(hw_host, torch.int32, hw.shape),
+                                    stream_ptr(canvases)), "augment_apply")

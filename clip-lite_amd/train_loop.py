@@ -198,7 +198,7 @@ class TrainStep:
                 and all(p.requires_grad for p in m.parameters()))
 
     def _capture(self, batch):
-        if not self._direct_ok() or any(k in batch for k in ("neg_input_ids", "aug_image", "aug_input_ids")):
+        if not self._direct_ok() or any(k in batch for k in ("neg_input_ids", "aug_image", "aug_image_plan", "aug_input_ids")):
             return self._capture_single(batch)
         from .bert import bert_backward, bert_forward
         from .loss import jsd_backward, jsd_forward
@@ -231,10 +231,19 @@ class TrainStep:
 
         # the image is staged (NCHW f32 -> padded NHWC4, one kernel) OUTSIDE the graphs, straight from the caller's tensor into the buffer the
         # captured stem reads: a replay then never copies the 77 MB batch into a static input first
-        from .resnet import stage_image
-        img0 = sb["image"].to(torch.float32).contiguous()
-        self._staged = (stage_image(rt, img0), img0.shape[2], img0.shape[3])
-        sb["image"] = torch.empty(img0.shape, dtype=sb["image"].dtype, device="meta")      # shape / dtype witness for _fits only
+        if "image_u8" in sb:
+            # a batch of the GPU-augmenting loader (DATA.GPU_AUGMENT): the augmentation kernels write the views of the caller's canvases
+            # straight into that buffer (augment.stage_views: a gray pass for the jittered views, then one launch) - no f32 image exists at all
+            from . import augment
+            S = self._view_size = augment.view_size(sb["image_plan"])
+            self._staged = (augment.stage_views(rt, sb["image_u8"], sb["image_hw"], sb["image_plan"], S), S, S)
+            for k in ("image_u8", "image_hw", "image_plan"):
+                sb[k] = torch.empty(sb[k].shape, dtype=sb[k].dtype, device="meta")
+        else:
+            from .resnet import stage_image
+            img0 = sb["image"].to(torch.float32).contiguous()
+            self._staged = (stage_image(rt, img0), img0.shape[2], img0.shape[3])
+            sb["image"] = torch.empty(img0.shape, dtype=sb["image"].dtype, device="meta")      # shape / dtype witness for _fits only
 
         def image_fwd():
             keep["img"], keep["ctx_i"] = resnet_forward(rt, m.image_encoder.img_encoder, None, True, staged=self._staged)
@@ -529,6 +538,11 @@ class TrainStep:
     def _capture_single(self, batch):
         rt = self.model.runtime
         self._static_batch = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in self._padded(batch).items()}
+        self._view_size = None
+        for k in ("image_plan", "neg_image_plan"):          # the view size is read here: inside the capture nothing may wait for the device
+            if k in batch:
+                from . import augment
+                self._view_size = augment.view_size(batch[k])
         self.optimizer.zero_grad()            # no-op after a completed step (the update kernel leaves the gradients zeroed)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
@@ -540,7 +554,10 @@ class TrainStep:
                 # branch the executors fork is ordered behind it) — the backward executors' own ensure_transposed() is a no-op under capture, and
                 # without this node every replay would run its dgrads against the weights of the last eager step
                 rt.arena.ensure_transposed(force=True, capturing=True)
-                out = self.model(self._static_batch)
+                sbatch = self._static_batch
+                if self._view_size is not None:
+                    sbatch = self.model.materialize_views(sbatch, size=self._view_size)
+                out = self.model(sbatch)
                 self.scaler.scale(out["loss"]).backward()
                 if self.exchange is None:
                     self._capture_update()
@@ -609,8 +626,12 @@ class TrainStep:
             if torch.is_tensor(v):
                 dst = self._static_batch[k]
                 if dst.device.type == "meta":           # the image: staged by one kernel into the buffer the captured stem reads
-                    from .resnet import stage_image
-                    stage_image(rt, v.to(torch.float32).contiguous(), out=self._staged[0])
+                    if k == "image":
+                        from .resnet import stage_image
+                        stage_image(rt, v.to(torch.float32).contiguous(), out=self._staged[0])
+                    elif k == "image_u8":               # (its two tables come with it)
+                        from . import augment
+                        augment.stage_views(rt, v, batch["image_hw"], batch["image_plan"], self._view_size, out=self._staged[0])
                     continue
                 on_side = feed is not None and k in self._CAPTION_KEYS
                 if on_side and v.is_cuda:

@@ -605,6 +605,34 @@ int clite_kmeans_accumulate(const float* X, int ldx, const int* assign, const fl
  * cluster.py:136-139. */
 int clite_kmeans_update(const void* work, uint64_t work_bytes, const int* counts, int N, int D, int K, float* C, int ldc, float* hc, void* stream);
 
+/* ---- Image augmentation on the device (reference factories.py:112-160 and data/dataloader.py:186-192, which run on the CPU; semantics:
+ * clip-lite_amd/augment.py). Additive to ABI v12. canvases: uint8 [N][cap], sample n an HWC image of hw[2n] x hw[2n+1] pixels packed at the front
+ * of its slot (pitch 3 w); hw: int32 [N][2]; plan: f32 [N][CLITE_AUGMENT_PLAN_W], one row per view: crop box x0, y0, cw, ch in canvas pixels,
+ * flip flag, jitter flag, brightness / contrast / saturation factors, hue shift, the order of the four colour ops (0 brightness, 1 contrast,
+ * 2 saturation, 3 hue), normalise flag, one unused column. A view is the box resampled to S x S with PIL's antialiased triangle filter, mirrored,
+ * jittered on [0, 255] values and scaled to [0, 1] or ImageNet-normalised; all in f32 with contraction off, identical in every entry below.
+ * plan_host / hw_host: optional host mirrors of the two tables, validated before anything is enqueued: -2 for a canvas extent that is not
+ * positive or does not fit cap, -3 for a row that is not finite, has an empty box, a box outside its canvas or an order that is no permutation,
+ * -4 for a box wider or higher than CLITE_AUGMENT_MAX_SCALE * S (the kernels read at most CLITE_AUGMENT_MAX_TAPS taps per axis). -1: a null
+ * pointer or a shape outside N in [1, 65535], S in [1, 4096]. Without the mirrors a bad table cannot fault either: such a view comes out
+ * blank (extent) or with clipped taps. */
+#define CLITE_AUGMENT_PLAN_W 16
+#define CLITE_AUGMENT_MAX_SCALE 4
+#define CLITE_AUGMENT_MAX_TAPS 9
+#define CLITE_AUGMENT_GRAY_BLOCKS(S) (((S) * (S) + 255) / 256)   /* partial sums per view of clite_augment_gray_mean */
+enum { CLITE_AUGMENT_NCHW = 0, CLITE_AUGMENT_NHWC4 = 1 };
+/* mean[n] (f32 [N]) = mean over the view of 0.299 R + 0.587 G + 0.114 B as the view stands in front of its contrast op; 0 for a view whose
+ * jitter flag is off (nothing of it is read). No float atomics: work (f32 [N][CLITE_AUGMENT_GRAY_BLOCKS(S)] scratch) receives one partial sum per
+ * workgroup and a second kernel adds them in order, so the result is bitwise reproducible and the same in both settings of
+ * clite_set_deterministic. */
+int clite_augment_gray_mean(const uint8_t* canvases, const int* hw, int64_t cap, const float* plan, int N, int S, float* mean, float* work,
+                            const float* plan_host, const int* hw_host, void* stream);
+/* form CLITE_AUGMENT_NCHW: out f32 [N][3][S][S] (dtype CLITE_F32; pad, Hp, Wp ignored) - the batch dict's "image". form CLITE_AUGMENT_NHWC4:
+ * out [N][Hp][Wp][4] in dtype, the view at (pad, pad), every other element (padding, channel 3) written as zero - exactly what
+ * clite_image_to_nhwc4 makes of the NCHW form. mean: what clite_augment_gray_mean left for the same tables (read only by views with jitter). */
+int clite_augment_apply(int form, int dtype, const uint8_t* canvases, const int* hw, int64_t cap, const float* plan, const float* mean, int N, int S,
+                        void* out, int pad, int Hp, int Wp, const float* plan_host, const int* hw_host, void* stream);
+
 /* ---- Update path (reference train.py:221-226, factories.py:464-482, optim/lookahead.py:88-101) over flat f32 buffers. */
 typedef struct clite_optim_item {   /* one workgroup's slice of one parameter tensor (never straddles tensors) */
   uint64_t start;                   /* element offset into the flat buffers, multiple of 4 */
