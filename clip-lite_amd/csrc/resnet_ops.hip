@@ -71,11 +71,11 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(clite_bn p, const T* __re
     float unb = p.M > 1 ? (float)p.M / (float)(p.M - 1) : 1.f;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      p.running_mean[c0 + e] = (1.f - p.momentum) * p.running_mean[c0 + e] + p.momentum * mean[e];
-      p.running_var[c0 + e] = (1.f - p.momentum) * p.running_var[c0 + e] + p.momentum * var[e] * unb;
+      p.running_mean[c0 + e] = bn_running(p.running_mean[c0 + e], p.momentum, mean[e], 1.f);
+      p.running_var[c0 + e] = bn_running(p.running_var[c0 + e], p.momentum, var[e], unb);
       if (res_affine) {
-        p.res_running_mean[c0 + e] = (1.f - p.momentum) * p.res_running_mean[c0 + e] + p.momentum * mr[e];
-        p.res_running_var[c0 + e] = (1.f - p.momentum) * p.res_running_var[c0 + e] + p.momentum * vr[e] * unb;
+        p.res_running_mean[c0 + e] = bn_running(p.res_running_mean[c0 + e], p.momentum, mr[e], 1.f);
+        p.res_running_var[c0 + e] = bn_running(p.res_running_var[c0 + e], p.momentum, vr[e], unb);
       }
     }
   }
@@ -504,8 +504,8 @@ __global__ __launch_bounds__(256) void stem_bn_pool_fwd_kernel(clite_bn p, const
     float unb = p.M > 1 ? (float)p.M / (float)(p.M - 1) : 1.f;
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-      p.running_mean[c0 + e] = (1.f - p.momentum) * p.running_mean[c0 + e] + p.momentum * mean[e];
-      p.running_var[c0 + e] = (1.f - p.momentum) * p.running_var[c0 + e] + p.momentum * var[e] * unb;
+      p.running_mean[c0 + e] = bn_running(p.running_mean[c0 + e], p.momentum, mean[e], 1.f);
+      p.running_var[c0 + e] = bn_running(p.running_var[c0 + e], p.momentum, var[e], unb);
     }
   }
   const int P = N * Ho * Wo;

@@ -50,6 +50,11 @@ DEV void bn_coef(const float* stats, int R, int RS, const float* gamma, const fl
 }
 
 
+// A running statistic after one momentum update: (1 - momentum) * old + momentum * batch * unbias. Written with an explicit fmaf so that every kernel
+// that performs the update rounds alike: left to the compiler, bn_apply_kernel and stem_bn_pool_fwd_kernel contracted the expression differently and
+// their running statistics differed in the last bit (tests/test_gpu_resnet_ops.py).
+DEV float bn_running(float old, float momentum, float batch, float unbias) { return fmaf(1.f - momentum, old, momentum * batch * unbias); }
+
 template <typename T> DEV void round_store_type(float (&v)[8]) { if constexpr (sizeof(T) == 2) round8_bf16(v); }
 
 // dz0 of one input pixel (8 channels): the pooled gradients of the <= 4 windows whose argmax is this pixel, rounded to the storage type,
