@@ -23,6 +23,19 @@ with the distributions and the draw order of data.load_image (crop scale and log
 flip with p = 0.5; jitter with p = 0.8, factors uniform in 1 +- x, hue in +-0.1, random order; the `::{kwargs}` syntax), drawn from the
 per-index generator `seed * 1000003 + idx`. `center_crop` yields the integer centred box at scale 1.
 
+Post (`plan_transforms(..., return_post=True)`): a second f32 row of POST_W columns per view, for the two transforms that follow the jitter -
+    POST_GRAY                            1: `random_gray` fired (reference factories.py: alb.ToGray, p = 0.2)
+    POST_BLUR                            1: `blur` fired (reference factories.py: alb.GaussianBlur, p = 0.5)
+    POST_W0 .. +3                        the blur's weights, centre outward (zeros without blur); two reserved zero columns follow
+Draws, in list order from the same generator, on both paths (data.load_image makes the same ones): `random_gray` one draw, applied if
+rnd() < p (default 0.2); `blur` one draw, applied if rnd() < p (default 0.5), and if applied one more, k = lo + int(rnd() (hi - lo + 1)) for
+blur_limit = (lo, hi) (default (3, 7)), an even k going up by one - so the default gives 3, 5, 7 with probabilities 1/5, 2/5, 2/5. lo and hi must
+be odd and lie in 3..7, and a `sigma_limit` other than 0 is refused (ValueError): the kernel is OpenCV's fixed one for sigma <= 0, k <= 7,
+    k = 3: 0.5, 0.25, 0, 0      k = 5: 0.375, 0.25, 0.0625, 0      k = 7: 0.28125, 0.21875, 0.109375, 0.03125      (centre outward)
+all dyadic, so exact in f32 and of sum 1. The host writes the weights, not k, into the row. Both names take `::{kwargs}` for p, `blur` also for
+blur_limit. Same distribution family as albumentations 1.0.0 over OpenCV 4.5; the draws come from this package's generator, so an individual
+image differs from an albumentations run with the same seed.
+
 Pixel function, for output pixel (oy, ox) of an S x S view (f32 throughout, no intermediate rounding, no fused multiply-add):
   1. ox <- S - 1 - ox if the flip flag is set.
   2. The crop box is resampled to S x S with PIL's antialiased triangle filter (Image.BILINEAR with reducing support), per axis: scale = c / S,
@@ -32,10 +45,18 @@ Pixel function, for output pixel (oy, ox) of an S x S view (f32 throughout, no i
   3. With jitter on, the four ops in the plan's order on values in [0, 255], clamped to [0, 255] after each: brightness v fb; contrast
      m + fc (v - m) with m the mean of gray = 0.299 R + 0.587 G + 0.114 B over the view as it stands in front of the contrast op; saturation
      g + fs (v - g) with the pixel's own gray g; hue RGB -> HSV (colorsys), h + fh mod 1, HSV -> RGB.
+  3b. Gray, when POST_GRAY is set: g = 0.299 R + 0.587 G + 0.114 B on the unrounded values of step 3, v = (g, g, g).
+  3c. Blur, when POST_BLUR is set: a separable 7-tap filter with the symmetric weights w[|i|] = POST_W0 + |i| on the S x S view as it stands
+     after 3 / 3b, the horizontal pass first, then the vertical one, each adding its taps in ascending offset -3 .. +3 from zero. A coordinate
+     outside the view takes OpenCV's default border REFLECT_101 (-1 -> 1, S -> S - 2; numpy.pad(mode="reflect")). A blurred view needs S >= 4.
   4. (v / 255 - mean) / std with the normalise flag, else v / 255.
-tests/augment_ref.py restates this in NumPy float64 and is the yardstick of the kernels. Deliberate differences from the CPU path: PIL rounds to
-uint8 after each of its two resize passes and after every colour op, and ImageEnhance.Contrast rounds its mean to an integer (measured differences:
-DESIGN.md section 7); random_resized_crop cuts from the canvas, not from the full-resolution file.
+The device path has this one order - crop, flip, jitter, gray, blur, normalise - whatever the list says: the planner refuses a list that names
+`random_gray` or `blur` ahead of a colour jitter or of the box transform (the colour ops are not linear); gray and blur commute up to rounding
+and may come in either order. The CPU path applies the list in its own order.
+tests/augment_ref.py restates this in NumPy float64 (tests/augment_post_ref.py adds 3b / 3c) and is the yardstick of the kernels. Deliberate
+differences from the CPU path: PIL rounds to uint8 after each of its two resize passes and after every colour op, ImageEnhance.Contrast rounds
+its mean to an integer, gray is PIL's integer `L` conversion and the blur rounds its result to uint8 (measured differences: DESIGN.md section 7
+and 3.3f); random_resized_crop cuts from the canvas, not from the full-resolution file.
 
 The evaluation command lines (retrieval.py, voc_clf.py, linear_clf.py, zero_shot.py, cluster.py) keep the CPU path: their datasets do not emit
 canvases.
@@ -47,9 +68,14 @@ import torch
 from . import hip
 from .hip import AUGMENT_MAX_SCALE as MAX_SCALE
 from .hip import AUGMENT_PLAN_W as PLAN_W
+from .hip import AUGMENT_POST_W as POST_W
 
 PLAN_X0, PLAN_Y0, PLAN_CW, PLAN_CH, PLAN_FLIP, PLAN_JITTER, PLAN_FB, PLAN_FC, PLAN_FS, PLAN_FH, PLAN_ORDER, PLAN_NORMALIZE, PLAN_VIEW_SIZE = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 14, 15
 OP_BRIGHTNESS, OP_CONTRAST, OP_SATURATION, OP_HUE = 0, 1, 2, 3
+POST_GRAY, POST_BLUR, POST_W0 = 0, 1, 2
+POST_NAMES = ("random_gray", "blur")
+BLUR_WEIGHTS = {3: (0.5, 0.25, 0.0, 0.0), 5: (0.375, 0.25, 0.0625, 0.0), 7: (0.28125, 0.21875, 0.109375, 0.03125)}      # centre outward
+BLUR_MIN_VIEW = 4     # REFLECT_101 of a 3-pixel reach
 TRIM = 1.5            # longer side of a canvas <= floor(TRIM * shorter side)
 
 
@@ -93,11 +119,43 @@ def synthetic_canvas(short_side: int, generator):
     return torch.randint(0, 256, (short_side, short_side, 3), generator=generator, dtype=torch.uint8).numpy()
 
 
-def plan_transforms(h: int, w: int, transforms, crop_size: int, generator=None):
+def needs_post(transforms) -> bool:
+    """The list names `random_gray` or `blur`: its views need a post row beside the plan row."""
+    return any(spec.partition("::")[0] in POST_NAMES for spec in transforms)
+
+
+def draw_gray(rnd, kw) -> bool:
+    """The draw of `random_gray` (one), shared by both paths."""
+    return rnd() < kw.get("p", 0.2)
+
+
+def draw_blur(rnd, kw) -> int:
+    """The draws of `blur` (one, and one more when it fires), shared by both paths: the kernel size 3, 5 or 7, or 0 when it does not fire."""
+    if kw.get("sigma_limit", 0) not in (0, (0, 0), [0, 0]):
+        raise ValueError(f"blur: sigma_limit {kw['sigma_limit']!r} is not supported (only 0: OpenCV's fixed kernels)")
+    lim = kw.get("blur_limit", (3, 7))
+    if not isinstance(lim, (tuple, list)) or len(lim) != 2:
+        raise ValueError(f"blur: blur_limit {lim!r} must be a pair (lo, hi)")
+    lo, hi = lim
+    if not all(isinstance(x, int) and x % 2 == 1 and 3 <= x <= 7 for x in (lo, hi)) or lo > hi:
+        raise ValueError(f"blur: blur_limit {lim!r} must be odd sizes in 3..7, (lo, hi) with lo <= hi")
+    if rnd() >= kw.get("p", 0.5):
+        return 0
+    k = lo + int(rnd() * (hi - lo + 1))
+    return k + 1 if k % 2 == 0 else k
+
+
+def plan_transforms(h: int, w: int, transforms, crop_size: int, generator=None, return_post=False):
     """One plan row (f32 [PLAN_W]) for a view of an h x w canvas through the named transforms, with load_image's distributions and draw order.
     `smallest_resize` is the worker's (make_canvas) and draws nothing; `global_resize` takes the whole canvas; at most one of the box
-    transforms (center_crop, random_resized_crop, global_resize) may appear. Raises ValueError for a plan the kernels refuse (check_plan)."""
+    transforms (center_crop, random_resized_crop, global_resize) may appear. Raises ValueError for a plan the kernels refuse (check_plan).
+    return_post: return (row, post row [POST_W]) - required for a list that names `random_gray` or `blur` (ValueError otherwise: neither is
+    dropped silently), which must name them behind its box transform and its colour jitter."""
     from .data import _transform_args
+    if not return_post and needs_post(transforms):
+        raise ValueError("the transform list names random_gray / blur: its views need a post row (plan_transforms(..., return_post=True))")
+    post = torch.zeros(POST_W, dtype=torch.float32)
+    post_seen = None
 
     def rnd():
         return float(torch.rand((), generator=generator))
@@ -111,6 +169,8 @@ def plan_transforms(h: int, w: int, transforms, crop_size: int, generator=None):
         size, kw = _transform_args(arg, crop_size)
         if name == "smallest_resize":
             continue
+        if post_seen and name in ("global_resize", "center_crop", "random_resized_crop", "color_jitter", "color_jitter8"):
+            raise ValueError(f"GPU augmentation applies gray and blur after the crop and the colour jitter; {post_seen!r} stands ahead of {spec!r}")
         if name in ("global_resize", "center_crop", "random_resized_crop"):
             if box is not None:
                 raise ValueError(f"GPU augmentation takes one crop / resize transform per view; {spec!r} is a second one")
@@ -150,6 +210,20 @@ def plan_transforms(h: int, w: int, transforms, crop_size: int, generator=None):
                 order = sorted(range(4), key=lambda _: rnd())
                 row[PLAN_JITTER] = 1.0
                 row[PLAN_FB], row[PLAN_FC], row[PLAN_FS], row[PLAN_FH] = fb, fc, fs, fh
+        elif name == "random_gray":
+            post_seen = post_seen or spec
+            if draw_gray(rnd, kw):
+                post[POST_GRAY] = 1.0
+        elif name == "blur":
+            post_seen = post_seen or spec
+            if post[POST_BLUR] != 0:
+                raise ValueError("GPU augmentation takes one blur per view")
+            k = draw_blur(rnd, kw)
+            if k:
+                if crop_size < BLUR_MIN_VIEW:
+                    raise ValueError(f"a blurred view needs IMAGE_CROP_SIZE >= {BLUR_MIN_VIEW}")
+                post[POST_BLUR] = 1.0
+                post[POST_W0:POST_W0 + 4] = torch.tensor(BLUR_WEIGHTS[k])
         elif name == "normalize":
             row[PLAN_NORMALIZE] = 1.0
         else:
@@ -162,6 +236,9 @@ def plan_transforms(h: int, w: int, transforms, crop_size: int, generator=None):
     row[PLAN_ORDER:PLAN_ORDER + 4] = torch.tensor(order, dtype=torch.float32)
     row[PLAN_VIEW_SIZE] = float(crop_size)
     check_plan(row[None], torch.tensor([[h, w]]), crop_size)
+    if return_post:
+        check_post(post[None], crop_size)
+        return row, post
     return row
 
 
@@ -182,6 +259,26 @@ def check_plan(plan, hw, S: int):
                          f"{2 * MAX_SCALE + 1} taps per axis (use a smaller DATA.GPU_AUGMENT_SOURCE_SIZE)")
     if bool((plan[:, PLAN_ORDER:PLAN_ORDER + 4].sort(dim=1).values != torch.arange(4.0)).any()):
         raise ValueError("the colour-op order of a plan row is not a permutation of 0..3")
+
+
+def check_post(post, S: int):
+    """Host-side refusal of post rows the kernel does not take: a flag that is not 0 or 1, a weight that is not finite or is negative, and
+    on a blurred row weights that do not sum to 1 or a view smaller than BLUR_MIN_VIEW."""
+    post = torch.as_tensor(post, dtype=torch.float32)
+    if post.dim() != 2 or post.shape[1] != POST_W:
+        raise ValueError(f"post must be [N][{POST_W}]")
+    flags, wt = post[:, [POST_GRAY, POST_BLUR]], post[:, POST_W0:POST_W0 + 4]
+    if bool(((flags != 0) & (flags != 1)).any()):
+        raise ValueError("a gray / blur flag of a post row is not 0 or 1")
+    if not bool(torch.isfinite(wt).all()) or bool((wt < 0).any()):
+        raise ValueError("the blur weights of a post row must be finite and not negative")
+    blurred = post[:, POST_BLUR] != 0
+    if bool(blurred.any()):
+        if S < BLUR_MIN_VIEW:
+            raise ValueError(f"a blurred view needs S >= {BLUR_MIN_VIEW}")
+        total = wt[:, 0] + 2.0 * (wt[:, 1] + wt[:, 2] + wt[:, 3])
+        if bool(((total - 1.0).abs() > 1e-3)[blurred].any()):
+            raise ValueError("the blur weights of a post row do not sum to 1")
 
 
 def view_size(plan) -> int:
@@ -213,18 +310,23 @@ def gray_means(image_u8, image_hw, plan, S: int, plan_host=None, hw_host=None):
     return mean
 
 
-def views(image_u8, image_hw, plan, S: int, plan_host=None, hw_host=None):
-    """The batch-dict form: f32 NCHW [N][3][S][S] views of device canvases."""
+def views(image_u8, image_hw, plan, S: int, plan_host=None, hw_host=None, post=None, post_host=None):
+    """The batch-dict form: f32 NCHW [N][3][S][S] views of device canvases. post: the views' gray / blur rows (None: neither, the plain
+    entry point)."""
     image_u8, image_hw, plan = image_u8.contiguous(), image_hw.contiguous(), plan.contiguous()
     mean = gray_means(image_u8, image_hw, plan, S, plan_host, hw_host)
     out = torch.empty(image_u8.shape[0], 3, S, S, device=image_u8.device, dtype=torch.float32)
-    hip.augment_apply(hip.AUGMENT_NCHW, hip.F32, image_u8, image_hw, plan, mean, S, out, plan_host=plan_host, hw_host=hw_host)
+    if post is None:
+        hip.augment_apply(hip.AUGMENT_NCHW, hip.F32, image_u8, image_hw, plan, mean, S, out, plan_host=plan_host, hw_host=hw_host)
+    else:
+        hip.augment_apply_post(hip.AUGMENT_NCHW, hip.F32, image_u8, image_hw, plan, post.contiguous(), mean, S, out, plan_host=plan_host,
+                               hw_host=hw_host, post_host=post_host)
     return out
 
 
-def stage_views(rt, image_u8, image_hw, plan, S: int, out=None):
+def stage_views(rt, image_u8, image_hw, plan, S: int, out=None, post=None):
     """The stem form, what resnet.stage_image makes of `views(...)`: padded NHWC4 in the compute dtype. `out` re-uses an earlier result's
-    storage (the captured train step stages every batch into the buffer its graphs read)."""
+    storage (the captured train step stages every batch into the buffer its graphs read). post: as in `views`."""
     from .resnet import _alloc
     image_u8, image_hw, plan = image_u8.contiguous(), image_hw.contiguous(), plan.contiguous()
     N = image_u8.shape[0]
@@ -233,5 +335,8 @@ def stage_views(rt, image_u8, image_hw, plan, S: int, out=None):
     xpad = _alloc(rt, N, Hp, Wp, 4) if out is None else out
     assert tuple(xpad.shape) == (N, Hp, Wp, 4) and xpad.dtype == rt.tdtype
     mean = gray_means(image_u8, image_hw, plan, S)
-    hip.augment_apply(hip.AUGMENT_NHWC4, rt.dt, image_u8, image_hw, plan, mean, S, xpad, 3, Hp, Wp)
+    if post is None:
+        hip.augment_apply(hip.AUGMENT_NHWC4, rt.dt, image_u8, image_hw, plan, mean, S, xpad, 3, Hp, Wp)
+    else:
+        hip.augment_apply_post(hip.AUGMENT_NHWC4, rt.dt, image_u8, image_hw, plan, post.contiguous(), mean, S, xpad, 3, Hp, Wp)
     return xpad

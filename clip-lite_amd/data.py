@@ -17,7 +17,7 @@ same [CLS] ... [SEP] framing.
 Image source: when a record's image file exists it is decoded with PIL and put through the reference's transforms by name
 (`DATA.IMAGE_TRANSFORM_{TRAIN,VAL}`; factories.py:112-160): smallest_resize (shorter side -> 256 for DEFAULT_IMAGE_TRANSFORM, else the
 crop size), center_crop, random_resized_crop (scale 0.2-1), horizontal_flip (which also swaps "left" / "right" in the caption), color_jitter,
-normalize (ImageNet mean / std on [0, 1] pixels), HWC -> CHW float32
+random_gray, blur, normalize (ImageNet mean / std on [0, 1] pixels), HWC -> CHW float32
 (data/dataloader.py:186-192). A record whose file is missing gets a seeded synthetic image (the mock json of the reference points at
 files that exist on no machine we have).
 """
@@ -150,12 +150,33 @@ def _color_jitter(img, rnd, brightness=0.4, contrast=0.4, saturation=0.4, hue=0.
     return img
 
 
-def load_image(path: str, transforms, crop_size: int, generator=None, return_flipped=False):
+def _gaussian_blur(img, weights):
+    """The reference's `blur` once it fires (factories.py: albumentations GaussianBlur over cv2.GaussianBlur with sigma 0) on a PIL image, in
+    NumPy: the separable 7-tap filter with the symmetric `weights` (centre outward; augment.BLUR_WEIGHTS, OpenCV's fixed kernels), border
+    REFLECT_101, the horizontal pass then the vertical one in f32 (exact: the weights are dyadic), rounded back to uint8."""
+    from PIL import Image
+    import numpy as np
+    a = np.asarray(img, dtype=np.float32)
+    h, w = a.shape[:2]
+    if min(h, w) < 4:
+        raise ValueError(f"blur of a {h} x {w} image: the reflected border needs at least 4 pixels per side")
+    taps = [weights[abs(i)] for i in range(-3, 4)]
+    p = np.pad(a, ((0, 0), (3, 3), (0, 0)), mode="reflect")
+    a = sum(np.float32(t) * p[:, i:i + w] for i, t in enumerate(taps))
+    p = np.pad(a, ((3, 3), (0, 0), (0, 0)), mode="reflect")
+    a = sum(np.float32(t) * p[i:i + h] for i, t in enumerate(taps))
+    return Image.fromarray(np.clip(np.rint(a), 0, 255).astype(np.uint8), "RGB")
+
+
+def load_image(path: str, transforms, crop_size: int, generator=None, return_flipped=False, decisions=None):
     """PIL decode -> RGB -> the named transforms -> f32 CHW (reference data/dataloader.py:186-192 with the transform table of
     factories.py:112-160). Names may carry arguments as "name::{kwargs dict}" (the reference's syntax, factories.py:112-115) or "name::size";
     factories.py:213-221 passes the crop size to the resize / crop transforms. Random transforms draw from `generator` (a torch.Generator) so
     that a dataset index is reproducible. return_flipped: also return whether `horizontal_flip` fired — the reference's flip swaps "left" and
-    "right" in the caption of a flipped image (data/transforms.py:156-181), which the dataset applies before tokenising."""
+    "right" in the caption of a flipped image (data/transforms.py:156-181), which the dataset applies before tokenising.
+    `random_gray` (factories.py: alb.ToGray, p = 0.2) and `blur` (alb.GaussianBlur, p = 0.5, blur_limit (3, 7)) draw as augment.py's docstring
+    says, the same draws as the GPU path's planner. decisions: a dict that receives what the random transforms decided ("flipped", "gray",
+    "blur": the kernel size or 0)."""
     from PIL import Image
     import numpy as np
     img = Image.open(path).convert("RGB")
@@ -163,7 +184,7 @@ def load_image(path: str, transforms, crop_size: int, generator=None, return_fli
     def rnd():
         return float(torch.rand((), generator=generator))
 
-    normalized, flipped = False, False
+    normalized, flipped, gray, blur_k = False, False, False, 0
     for spec in transforms:
         name, _, arg = spec.partition("::")
         size, kw = _transform_args(arg, crop_size)
@@ -202,10 +223,23 @@ def load_image(path: str, transforms, crop_size: int, generator=None, return_fli
         elif name in ("color_jitter", "color_jitter8"):
             x = 0.8 if name == "color_jitter8" else 0.4
             img = _color_jitter(img, rnd, kw.get("brightness", x), kw.get("contrast", x), kw.get("saturation", x), kw.get("hue", 0.1), kw.get("p", 0.8))
+        elif name == "random_gray":
+            from . import augment
+            if augment.draw_gray(rnd, kw):
+                img = img.convert("L").convert("RGB")
+                gray = True
+        elif name == "blur":
+            from . import augment
+            k = augment.draw_blur(rnd, kw)
+            if k:
+                img = _gaussian_blur(img, augment.BLUR_WEIGHTS[k])
+                blur_k = k
         elif name == "normalize":
             normalized = True
         else:
             raise KeyError(f"unknown image transform {spec!r}")
+    if decisions is not None:
+        decisions.update(flipped=flipped, gray=gray, blur=blur_k)
     x = torch.from_numpy(np.asarray(img, dtype=np.float32).copy()) / 255.0          # HWC in [0, 1]
     if normalized:                               # albumentations Normalize(mean, std, max_pixel_value=255)
         x = (x - torch.tensor(IMAGENET_COLOR_MEAN)) / torch.tensor(IMAGENET_COLOR_STD)
@@ -267,11 +301,14 @@ class _CaptionDataset(Dataset):
         else:
             canvas = augment.synthetic_canvas(self.canvas_side, g)
         h, w = canvas.shape[:2]
-        plan = augment.plan_transforms(h, w, self.image_transform, self.image_size, g)
-        out = {"image_u8": torch.from_numpy(canvas), "image_plan": plan}
-        if self.visual_ssl:
-            out["aug_image_plan"] = augment.plan_transforms(h, w, self.image_transform, self.image_size, g)
-        return out, bool(plan[augment.PLAN_FLIP] != 0)
+        post = augment.needs_post(self.image_transform)          # random_gray / blur: a post row beside every plan row
+        out = {"image_u8": torch.from_numpy(canvas)}
+        for pre in ("", "aug_") if self.visual_ssl else ("",):
+            rows = augment.plan_transforms(h, w, self.image_transform, self.image_size, g, return_post=post)
+            out[pre + "image_plan"] = rows[0] if post else rows
+            if post:
+                out[pre + "image_post"] = rows[1]
+        return out, bool(out["image_plan"][augment.PLAN_FLIP] != 0)
 
     def __getitem__(self, idx):
         g = torch.Generator().manual_seed(self.seed * 1000003 + idx)
@@ -320,6 +357,10 @@ class _CaptionDataset(Dataset):
                 if k in items[0]:
                     batch[k] = torch.stack([i[k] for i in items])
                     augment.check_plan(batch[k], batch["image_hw"], self.image_size)
+            for k in ("image_post", "aug_image_post"):
+                if k in items[0]:
+                    batch[k] = torch.stack([i[k] for i in items])
+                    augment.check_post(batch[k], self.image_size)
         else:
             batch["image"] = torch.stack([i["image"] for i in items])
             if "aug_image" in items[0]:
@@ -472,7 +513,7 @@ class ClusteredDataset(Dataset):
         idx = int(idx)
         item = self.base[idx]
         neg = self.base[self.negative_index(idx)]
-        for k in ("image", "image_u8", "image_plan", "caption_tokens"):          # (a GPU-augmenting base: the negative's canvas and plan row)
+        for k in ("image", "image_u8", "image_plan", "image_post", "caption_tokens"):          # (a GPU-augmenting base: the negative's canvas and rows)
             if k in neg:
                 item["neg_" + k] = neg[k]
         return item
@@ -481,7 +522,7 @@ class ClusteredDataset(Dataset):
         batch = self.base.collate_fn(items)
         negs = [{"image_id": i["image_id"], **{k[4:]: v for k, v in i.items() if k.startswith("neg_")}} for i in items]
         nb = self.base.collate_fn(negs)               # the negatives' captions are padded to their own longest row (data/dataloader.py:778-790)
-        for k in ("image", "image_u8", "image_hw", "image_plan", "input_ids", "attention_mask"):
+        for k in ("image", "image_u8", "image_hw", "image_plan", "image_post", "input_ids", "attention_mask"):
             if k in nb:
                 batch["neg_" + k] = nb[k]
         return batch

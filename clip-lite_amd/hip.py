@@ -158,6 +158,7 @@ _SIGNATURES = {
     "clite_kmeans_update": [_V, _U64, _V, _I, _I, _I, _V, _I, _V, _V],
     "clite_augment_gray_mean": [_V, _V, C.c_int64, _V, _I, _I, _V, _V, _V, _V, _V],
     "clite_augment_apply": [_I, _I, _V, _V, C.c_int64, _V, _V, _I, _I, _V, _I, _I, _I, _V, _V, _V],
+    "clite_augment_apply_post": [_I, _I, _V, _V, C.c_int64, _V, _V, _V, _I, _I, _V, _I, _I, _I, _V, _V, _V, _V],
     "clite_critic_jsd_bwd": [_I, _V, _V, _V, _V, _V, _F, _I, _I, _V, _V, _V, _V, _V, _V],
     "clite_prior_tail_fwd": [_I, _V, _V, _V, _I, _I, _I, _V, _V, _V],
     "clite_prior_tail_bwd": [_I, _V, _V, _V, _V, _F, _I, _I, _V, _V, _V, _V],
@@ -987,6 +988,7 @@ def kmeans_update(work, counts, N, D, K, Cm, ldc, hc):
 
 # ------------------------------------------------------------------------------------------------ image augmentation (clip_lite_amd/augment.py)
 AUGMENT_PLAN_W, AUGMENT_MAX_SCALE = 16, 4
+AUGMENT_POST_W = 8
 AUGMENT_NCHW, AUGMENT_NHWC4 = 0, 1
 
 
@@ -1033,3 +1035,16 @@ def augment_apply(form, dt, canvases, hw, plan, mean, S, out, pad=0, Hp=0, Wp=0,
     check(lib().clite_augment_apply(form, dt, p(canvases), p(hw), cap, p(plan), p(mean), N, S, p(out), pad, Hp, Wp,
                                     _host_ptr(plan_host, torch.float32, plan.shape), _host_ptr(hw_host, torch.int32, hw.shape),
                                     stream_ptr(canvases)), "augment_apply")
+
+
+def augment_apply_post(form, dt, canvases, hw, plan, post, mean, S, out, pad=0, Hp=0, Wp=0, plan_host=None, hw_host=None, post_host=None):
+    """augment_apply with the gray / blur table `post` (f32 [N][AUGMENT_POST_W]; include/clite.h: clite_augment_apply_post)."""
+    N, cap = _augment_tables(canvases, hw, plan)
+    if post.dtype != torch.float32 or tuple(post.shape) != (N, AUGMENT_POST_W) or not post.is_contiguous() or post.device != plan.device:
+        raise ValueError(f"augment: post must be a contiguous f32 [N][{AUGMENT_POST_W}] tensor beside the plan")
+    want = (N, 3, S, S) if form == AUGMENT_NCHW else (N, Hp, Wp, 4)
+    if tuple(out.shape) != want or out.dtype != TORCH_DTYPE[dt] or not out.is_contiguous() or mean.dtype != torch.float32 or mean.numel() < N:
+        raise ValueError(f"augment_apply_post: out must be a contiguous {TORCH_DTYPE[dt]} tensor of shape {want}")
+    check(lib().clite_augment_apply_post(form, dt, p(canvases), p(hw), cap, p(plan), p(post), p(mean), N, S, p(out), pad, Hp, Wp,
+                                         _host_ptr(plan_host, torch.float32, plan.shape), _host_ptr(hw_host, torch.int32, hw.shape),
+                                         _host_ptr(post_host, torch.float32, post.shape), stream_ptr(canvases)), "augment_apply_post")

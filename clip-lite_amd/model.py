@@ -68,20 +68,21 @@ class VLInfoModel(nn.Module):
     @staticmethod
     def materialize_views(batch, size=None):
         """A batch of the GPU-augmenting loader (DATA.GPU_AUGMENT: `image_u8`, `image_hw`, `image_plan`, with MODEL.VISUAL.SELF_SUPERVISED also
-        `aug_image_plan`; the same under the `neg_` prefix from ClusteredDataset) -> the batch with `image` / `aug_image` / `neg_image` made by the
+        `aug_image_plan`, with random_gray / blur in the transform list `image_post` / `aug_image_post` beside the plans; the same under the `neg_`
+        prefix from ClusteredDataset) -> the batch with `image` / `aug_image` / `neg_image` made by the
         augmentation kernels (augment.views). Any other batch is returned as it is."""
         if "image_u8" not in batch and "neg_image_u8" not in batch:
             return batch
         from . import augment
-        out = {k: v for k, v in batch.items() if not k.endswith(("image_u8", "image_hw", "image_plan"))}
+        out = {k: v for k, v in batch.items() if not k.endswith(("image_u8", "image_hw", "image_plan", "image_post"))}
         for pre in ("", "neg_"):
             if pre + "image_u8" not in batch:
                 continue
             u8, hw = batch[pre + "image_u8"], batch[pre + "image_hw"]
             S = size or augment.view_size(batch[pre + "image_plan"])
-            out[pre + "image"] = augment.views(u8, hw, batch[pre + "image_plan"], S)
+            out[pre + "image"] = augment.views(u8, hw, batch[pre + "image_plan"], S, post=batch.get(pre + "image_post"))
             if pre + "aug_image_plan" in batch:
-                out[pre + "aug_image"] = augment.views(u8, hw, batch[pre + "aug_image_plan"], S)
+                out[pre + "aug_image"] = augment.views(u8, hw, batch[pre + "aug_image_plan"], S, post=batch.get(pre + "aug_image_post"))
         if "aug_image_plan" in batch and "aug_image" not in out:
             raise KeyError("aug_image_plan without image_u8")
         return out

@@ -236,8 +236,8 @@ class TrainStep:
             # straight into that buffer (augment.stage_views: a gray pass for the jittered views, then one launch) - no f32 image exists at all
             from . import augment
             S = self._view_size = augment.view_size(sb["image_plan"])
-            self._staged = (augment.stage_views(rt, sb["image_u8"], sb["image_hw"], sb["image_plan"], S), S, S)
-            for k in ("image_u8", "image_hw", "image_plan"):
+            self._staged = (augment.stage_views(rt, sb["image_u8"], sb["image_hw"], sb["image_plan"], S, post=sb.get("image_post")), S, S)
+            for k in ("image_u8", "image_hw", "image_plan") + (("image_post",) if "image_post" in sb else ()):
                 sb[k] = torch.empty(sb[k].shape, dtype=sb[k].dtype, device="meta")
         else:
             from .resnet import stage_image
@@ -629,9 +629,10 @@ class TrainStep:
                     if k == "image":
                         from .resnet import stage_image
                         stage_image(rt, v.to(torch.float32).contiguous(), out=self._staged[0])
-                    elif k == "image_u8":               # (its two tables come with it)
+                    elif k == "image_u8":               # (its tables come with it)
                         from . import augment
-                        augment.stage_views(rt, v, batch["image_hw"], batch["image_plan"], self._view_size, out=self._staged[0])
+                        augment.stage_views(rt, v, batch["image_hw"], batch["image_plan"], self._view_size, out=self._staged[0],
+                                            post=batch.get("image_post"))
                     continue
                 on_side = feed is not None and k in self._CAPTION_KEYS
                 if on_side and v.is_cuda:

@@ -632,6 +632,18 @@ int clite_augment_gray_mean(const uint8_t* canvases, const int* hw, int64_t cap,
  * clite_image_to_nhwc4 makes of the NCHW form. mean: what clite_augment_gray_mean left for the same tables (read only by views with jitter). */
 int clite_augment_apply(int form, int dtype, const uint8_t* canvases, const int* hw, int64_t cap, const float* plan, const float* mean, int N, int S,
                         void* out, int pad, int Hp, int Wp, const float* plan_host, const int* hw_host, void* stream);
+/* clite_augment_apply with the two transforms that follow the colour jitter (augment.py steps 3b / 3c). Additive to ABI v12. post: f32
+ * [N][CLITE_AUGMENT_POST_W], one row per view: gray flag (R = G = B = 0.299 R + 0.587 G + 0.114 B), blur flag, the weights w0..w3 of a symmetric
+ * separable 7-tap filter (w[|i|], horizontal pass then vertical, taps added in ascending offset, border REFLECT_101 on the S x S view), two
+ * reserved zeros. The host puts the weights of its kernel size into the row; the kernel holds no table. Gray comes first, then blur, then the
+ * normalisation. A row of zeros gives what clite_augment_apply gives, bit for bit. mean is clite_augment_gray_mean's of the same plan: both
+ * transforms follow the jitter, so the contrast mean does not see them. post_host: optional host mirror, validated with the other two: -3 for
+ * a flag that is not 0 or 1, a weight that is not finite or is negative, and on a blurred row for |w0 + 2 (w1 + w2 + w3) - 1| > 1e-3 or S < 4;
+ * -1 for a null post. Without the mirror a bad row cannot fault: a reflected coordinate is also clamped to [0, S - 1]. */
+#define CLITE_AUGMENT_POST_W 8
+int clite_augment_apply_post(int form, int dtype, const uint8_t* canvases, const int* hw, int64_t cap, const float* plan, const float* post,
+                             const float* mean, int N, int S, void* out, int pad, int Hp, int Wp, const float* plan_host, const int* hw_host,
+                             const float* post_host, void* stream);
 
 /* ---- Update path (reference train.py:221-226, factories.py:464-482, optim/lookahead.py:88-101) over flat f32 buffers. */
 typedef struct clite_optim_item {   /* one workgroup's slice of one parameter tensor (never straddles tensors) */

@@ -1,7 +1,8 @@
 """GPU augmentation beside what it replaces (README.md "Augmenting on the GPU"): at N = 128, S = 224 and 256 x 341 canvases the gray pass, the
 apply in the stem form and image_to_nhwc4 (the staging kernel of the f32 path), timed with device events in one process; and loader samples/s
 per worker for the CPU recipe (data.load_image) and the canvas recipe (augment.make_canvas + plan_transforms) on a generated 640 x 480 JPEG.
-Prints one JSON line. python tools/bench_augment.py [--reps 50]"""
+--post adds `apply_post_stem_us`: clite_augment_apply_post on the same tables in the same stem form with every view gray and blurred at k = 7 (the
+tiled LDS kernel's worst case), next to `apply_stem_us` from the same process. Prints one JSON line. python tools/bench_augment.py [--reps 50] [--post]"""
 import argparse
 import json
 import os
@@ -35,6 +36,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--loader-samples", type=int, default=40)
+    ap.add_argument("--post", action="store_true", help="also time clite_augment_apply_post with every view gray and blurred at k = 7")
     a = ap.parse_args()
     if not torch.cuda.is_available():
         raise RuntimeError("bench_augment.py times kernels on the GPU; there is none")
@@ -56,6 +58,14 @@ def main():
            "apply_nchw_us": timed(lambda: hip.augment_apply(hip.AUGMENT_NCHW, hip.F32, u8, hw, plan, mean, S, f32), a.reps),
            "image_to_nhwc4_us": timed(lambda: hip.image_to_nhwc4(hip.BF16, f32, xpad, N, S, S, 3, Hp, Wp), a.reps),
            "bytes_in": int(N * h * w * 3), "bytes_out_stem": int(xpad.numel() * 2)}
+    if a.post:
+        post = torch.zeros(N, augment.POST_W)
+        post[:, augment.POST_GRAY] = post[:, augment.POST_BLUR] = 1.0
+        post[:, augment.POST_W0:augment.POST_W0 + 4] = torch.tensor(augment.BLUR_WEIGHTS[7])
+        post = post.cuda()
+        out["apply_post_stem_us"] = timed(lambda: hip.augment_apply_post(hip.AUGMENT_NHWC4, hip.BF16, u8, hw, plan, post, mean, S, xpad, 3, Hp, Wp),
+                                          a.reps)
+        out["post_over_plain"] = out["apply_post_stem_us"] / out["apply_stem_us"]
     from PIL import Image
     with tempfile.TemporaryDirectory() as d:
         path = os.path.join(d, "img.jpg")
