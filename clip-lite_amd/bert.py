@@ -75,6 +75,12 @@ class BertLayer(nn.Module):
         self.intermediate = _Intermediate(h, inner)
         self.output = _SelfOutput(inner, h, eps)
 
+    def attn_parts(self):
+        """(query, key, value, output projection, LayerNorm behind it): the executor's view of the attention block, whatever the checkpoint names
+        (mpnet.MPNetLayer returns its attention.attn.{q,k,v,o} / attention.LayerNorm here)."""
+        sa, so = self.attention.self, self.attention.output
+        return sa.query, sa.key, sa.value, so.dense, so.LayerNorm
+
 
 class _Embeddings(nn.Module):
     def __init__(self, vocab, h, max_pos, eps):
@@ -100,6 +106,8 @@ class _Pooler(nn.Module):
 class BertModel(nn.Module):
     """BertConfig defaults (transformers): hidden 768, 12 heads, intermediate 3072, vocab 30522, 512 positions, GELU(erf),
     LayerNorm eps 1e-12, hidden/attention dropout 0.1."""
+
+    kind = "bert"      # what bert_forward / bert_backward branch on (mpnet.MPNetModel: "mpnet")
 
     def __init__(self, num_hidden_layers=12, hidden=768, heads=12, inner=3072, vocab=30522, max_pos=512, dropout=0.1, eps=1e-12):
         super().__init__()
@@ -149,7 +157,10 @@ def _linear_grads(rt, lin, dy, x, M, dw=None, db=None, bias_done=False, defer=No
 
 
 def bert_forward(rt, net, input_ids, attention_mask, step):
-    """input_ids/attention_mask: int64 [B][L] on the device, L <= 32. Returns (pooler_output [B][H], ctx)."""
+    """input_ids/attention_mask: int64 [B][L] on the device, L <= 32. Returns (pooler_output [B][H], ctx).
+    net: BertModel, or mpnet.MPNetModel — the same executor with MPNet's four differences (mpnet.py): embeddings without token types and with
+    position ids counted from the ids, a relative-position bias (built here once per step from the trained table) in every layer's attention,
+    and the masked mean over the last layer's tokens as the output instead of the pooler."""
     B, L = input_ids.shape
     if L > 32:
         raise RuntimeError("clip_lite_amd: the attention kernel supports captions of at most 32 tokens (reference config.py:69: 30)")
@@ -163,11 +174,23 @@ def bert_forward(rt, net, input_ids, attention_mask, step):
     ids = input_ids.contiguous()
     mask = attention_mask.contiguous().to(torch.int64)
     emb = net.embeddings
+    mp = net.kind == "mpnet"
     s0 = _alloc(rt, M, Hd)
-    hip.embed_fwd(dt, ids, A.w(emb.word_embeddings.weight), A.w(emb.position_embeddings.weight), A.w(emb.token_type_embeddings.weight),
-                  s0, M, L, Hd, net.vocab)
+    pids = bias = None
+    if mp:
+        pids = torch.empty(M, device=rt.device, dtype=torch.int32)
+        hip.embed_mpnet_fwd(dt, ids, A.w(emb.word_embeddings.weight), A.w(emb.position_embeddings.weight), s0, pids, M, L, Hd, net.vocab, net.max_pos,
+                            net.padding_idx)
+        # the layers' shared additive bias [heads][32][32] from the f32 master of the trained table: once per step, inside a captured step
+        bias = torch.empty(heads * 32 * 32, device=rt.device, dtype=torch.float32)
+        hip.attention_bias_build(A.w32(net.encoder.relative_attention_bias.weight), net.bucket_table, bias, heads, L)
+    else:
+        hip.embed_fwd(dt, ids, A.w(emb.word_embeddings.weight), A.w(emb.position_embeddings.weight), A.w(emb.token_type_embeddings.weight),
+                      s0, M, L, Hd, net.vocab)
     # fp8 forward (BASELINE configs[4]; fp8.Fp8Text): QKV, FFN1 and FFN2 read e4m3 copies their producers wrote (LayerNorm forward, FFN1's epilogue)
     from .fp8 import text_state
+    if mp and rt.fp8_text and rt.lowp:
+        raise RuntimeError("clip_lite_amd: the fp8 forward (--fp8) is built for the BERT text encoder only; run the MPNet text encoder without it")
     f8 = text_state(rt, net)
     if f8 is not None:
         f8.begin_step()
@@ -186,24 +209,27 @@ def bert_forward(rt, net, input_ids, attention_mask, step):
     d0 = drop(p_h)
     q, h8 = prod(0, 0, Hd) if nl else (None, None)
     hip.layernorm_fwd(dt, s0, emb.LayerNorm.weight, emb.LayerNorm.bias, emb.LayerNorm.eps, h, st0, M, Hd, d0, fp8=q)
-    ctx = {"B": B, "L": L, "ids": ids, "mask": mask, "s0": s0, "st0": st0, "d0": d0, "layers": []}
+    ctx = {"B": B, "L": L, "ids": ids, "mask": mask, "s0": s0, "st0": st0, "d0": d0, "layers": [], "pids": pids, "bias": bias}
 
     for l, layer in enumerate(net.encoder.layer):
-        sa, so = layer.attention.self, layer.attention.output
-        wqkv = A.span([sa.query.weight, sa.key.weight, sa.value.weight])
-        bqkv = A.span([sa.query.bias, sa.key.bias, sa.value.bias], lowp=False)
+        wq, wk, wv, wo, ln1 = layer.attn_parts()
+        wqkv = A.span([wq.weight, wk.weight, wv.weight])
+        bqkv = A.span([wq.bias, wk.bias, wv.bias], lowp=False)
         qkv = _alloc(rt, M, 3 * Hd)
         linear(h, h8, wqkv, lambda: f8.weight(l, 0, (3 * Hd, Hd)), M, 3 * Hd, Hd, hip.epilogue(qkv, 3 * Hd, bias=bqkv))
         ctxt = _alloc(rt, M, Hd)
         da = drop(p_a)
-        hip.attention_fwd(dt, qkv, mask, ctxt, B, L, heads, da)
+        if mp:
+            hip.attention_bias_fwd(dt, qkv, mask, bias, ctxt, B, L, heads, da)
+        else:
+            hip.attention_fwd(dt, qkv, mask, ctxt, B, L, heads, da)
         s1 = _alloc(rt, M, Hd)
         d1 = drop(p_h)
-        hip.gemm_nt(dt, ctxt, A.w(so.dense.weight), M, Hd, Hd, hip.epilogue(s1, Hd, bias=so.dense.bias, drop=d1, residual=h))
+        hip.gemm_nt(dt, ctxt, A.w(wo.weight), M, Hd, Hd, hip.epilogue(s1, Hd, bias=wo.bias, drop=d1, residual=h))
         h1 = _alloc(rt, M, Hd)
         st1 = torch.empty(M, 2, device=rt.device, dtype=torch.float32)
         q, h18 = prod(l, 1, Hd)
-        hip.layernorm_fwd(dt, s1, so.LayerNorm.weight, so.LayerNorm.bias, so.LayerNorm.eps, h1, st1, M, Hd, fp8=q)
+        hip.layernorm_fwd(dt, s1, ln1.weight, ln1.bias, ln1.eps, h1, st1, M, Hd, fp8=q)
         f = _alloc(rt, M, inner)      # FFN pre-activation (kept for GELU')
         g = _alloc(rt, M, inner)
         q, g8 = prod(l, 2, inner)
@@ -227,6 +253,12 @@ def bert_forward(rt, net, input_ids, attention_mask, step):
     if f8 is not None and training:          # (an eval forward leaves the delayed-scaling state alone)
         f8.end_step()
     pooled = _alloc(rt, B, Hd)
+    if mp:
+        # sentence-transformers mean pooling (reference encoder.py:197-198): the pooler's parameters exist for checkpoint parity and take no part
+        ctx["inv"] = inv = torch.empty(B, device=rt.device, dtype=torch.float32)
+        hip.mean_pool_fwd(dt, h, mask, pooled, inv, B, L, Hd)
+        ctx["h_last"], ctx["pooled"] = h, pooled
+        return pooled, ctx
     hip.gemm_nt(dt, h, A.w(net.pooler.dense.weight), B, Hd, Hd, hip.epilogue(pooled, Hd, bias=net.pooler.dense.bias, act=hip.ACT_TANH, ws=rt.gemm_ws(B, Hd)), lda=L * Hd)
     ctx["h_last"], ctx["pooled"] = h, pooled
     return pooled, ctx
@@ -269,7 +301,15 @@ def bert_backward(rt, net, ctx, dpooled, defer=None, seg=None):
         defer = own_group = hip.WgradGroup(rt.dt)          # uncaptured backward: grouped launch at the end of this call
     staged, pooler_done = own_group is not None and getattr(rt, "exchange", None) is not None, False
     A.ensure_transposed(capturing=rt._capturing)
-    if first:
+    mp = net.kind == "mpnet"
+    if first and mp:
+        # mean pool: every token of the last layer receives mask * dy / count (BERT's pooler scatters into token 0 only)
+        dh = _alloc(rt, M, Hd)
+        hip.mean_pool_bwd(dt, dpooled, ctx["mask"], ctx["inv"], dh, B, L, Hd)
+        if own_group is None:
+            rt.grads_ready(net.pooler)
+        ctx["dbias_partials"] = torch.empty(max(nl, 1) * B * heads * 32, device=rt.device, dtype=torch.float32)
+    elif first:
         # pooler: dpre = dpooled * (1 - y^2); h[:, 0] rows only
         dpre = _alloc(rt, B, Hd)
         hip.tanh_bwd(dt, dpooled, ctx["pooled"], dpre, B * Hd)
@@ -286,8 +326,9 @@ def bert_backward(rt, net, ctx, dpooled, defer=None, seg=None):
         _dgrad(rt, dpre, B, Hd, Hd, hip.epilogue(dh, L * Hd, ws=rt.gemm_ws(B, Hd)), pw.weight)
     else:
         dh = ctx.pop("bwd_dh")
-    for (layer, h, qkv, ctxt, da, s1, d1, st1, h1, f, g, s2, d2, st2) in reversed(ctx["layers"][lo_layer:hi_layer]):
-        sa, so, out = layer.attention.self, layer.attention.output, layer.output
+    for li in reversed(range(lo_layer, hi_layer)):
+        (layer, h, qkv, ctxt, da, s1, d1, st1, h1, f, g, s2, d2, st2) = ctx["layers"][li]
+        (wq, wk, wv, wo, ln1), out = layer.attn_parts(), layer.output
         # LayerNorm 2 -> (dropout) -> FFN
         ds2 = _alloc(rt, M, Hd)
         ds2m = _alloc(rt, M, Hd) if d2[0] > 0 else None
@@ -308,18 +349,24 @@ def bert_backward(rt, net, ctx, dpooled, defer=None, seg=None):
         # LayerNorm 1 -> (dropout) -> attention output projection
         ds1 = _alloc(rt, M, Hd)
         ds1m = _alloc(rt, M, Hd) if d1[0] > 0 else None
-        hip.layernorm_bwd(dt, dh1, s1, st1, so.LayerNorm.weight, ds1, ds1m, A.g(so.LayerNorm.weight), A.g(so.LayerNorm.bias), M, Hd, drop_out=d1,
-                          dcolsum=A.g(so.dense.bias))
+        hip.layernorm_bwd(dt, dh1, s1, st1, ln1.weight, ds1, ds1m, A.g(ln1.weight), A.g(ln1.bias), M, Hd, drop_out=d1,
+                          dcolsum=A.g(wo.bias))
         dz1 = ds1m if ds1m is not None else ds1
-        _linear_grads(rt, so.dense, dz1, ctxt, M, bias_done=True, defer=defer)
+        _linear_grads(rt, wo, dz1, ctxt, M, bias_done=True, defer=defer)
         dctx = _alloc(rt, M, Hd)
-        _dgrad(rt, dz1, M, Hd, Hd, hip.epilogue(dctx, Hd), so.dense.weight)
+        _dgrad(rt, dz1, M, Hd, Hd, hip.epilogue(dctx, Hd), wo.weight)
         dqkv = _alloc(rt, M, 3 * Hd)
-        hip.attention_bwd(dt, qkv, ctx["mask"], dctx, dqkv, B, L, heads, da)
-        _linear_grads(rt, None, dqkv, h, M, dw=A.span([sa.query.weight, sa.key.weight, sa.value.weight], grad=True).view(3 * Hd, Hd),
-                      db=A.span([sa.query.bias, sa.key.bias, sa.value.bias], grad=True), defer=defer)
+        if mp:
+            # ... and this layer's [B*heads][32] bucket sums of dS: the gradient of the shared bias table, reduced once behind the first layer
+            n_part = B * heads * 32
+            hip.attention_bias_bwd(dt, qkv, ctx["mask"], ctx["bias"], net.bucket_table, dctx, dqkv, ctx["dbias_partials"][li * n_part:(li + 1) * n_part],
+                                   B, L, heads, da)
+        else:
+            hip.attention_bwd(dt, qkv, ctx["mask"], dctx, dqkv, B, L, heads, da)
+        _linear_grads(rt, None, dqkv, h, M, dw=A.span([wq.weight, wk.weight, wv.weight], grad=True).view(3 * Hd, Hd),
+                      db=A.span([wq.bias, wk.bias, wv.bias], grad=True), defer=defer)
         dhp = _alloc(rt, M, Hd)
-        _dgrad(rt, dqkv, M, Hd, 3 * Hd, hip.epilogue(dhp, Hd, residual=ds1), sa.query.weight, sa.key.weight, sa.value.weight)
+        _dgrad(rt, dqkv, M, Hd, 3 * Hd, hip.epilogue(dhp, Hd, residual=ds1), wq.weight, wk.weight, wv.weight)
         dh = dhp
         if own_group is None:
             rt.grads_ready(layer)
@@ -335,10 +382,22 @@ def bert_backward(rt, net, ctx, dpooled, defer=None, seg=None):
         return
     emb = net.embeddings
     ds0 = _alloc(rt, M, Hd)
-    hip.layernorm_bwd(dt, dh, ctx["s0"], ctx["st0"], emb.LayerNorm.weight, ds0, None, A.g(emb.LayerNorm.weight), A.g(emb.LayerNorm.bias), M, Hd,
-                      drop_in=ctx["d0"], dcolsum=A.g(emb.token_type_embeddings.weight)[0])      # token_type_ids = 0: every row adds to row 0
-    hip.embed_bwd(dt, ctx["ids"], ds0, A.g(emb.word_embeddings.weight), A.g(emb.position_embeddings.weight), M, L, Hd, net.vocab,
-                  padding_idx=0)      # HF BertEmbeddings: nn.Embedding(vocab, hidden, padding_idx=pad_token_id = 0)
+    if mp:
+        rel = net.encoder.relative_attention_bias.weight
+        if nl and rel.requires_grad:
+            hip.attention_bias_grad_reduce(ctx["dbias_partials"], A.g(rel), nl * B, heads)
+        if own_group is None or staged:
+            rt.grads_ready(net.encoder.relative_attention_bias)
+        hip.layernorm_bwd(dt, dh, ctx["s0"], ctx["st0"], emb.LayerNorm.weight, ds0, None, A.g(emb.LayerNorm.weight), A.g(emb.LayerNorm.bias), M, Hd,
+                          drop_in=ctx["d0"])
+        # both tables are nn.Embedding(..., padding_idx=1) in transformers: neither row 1 accumulates a gradient
+        hip.embed_mpnet_bwd(dt, ctx["ids"], ctx["pids"], ds0, A.g(emb.word_embeddings.weight), A.g(emb.position_embeddings.weight), M, L, Hd, net.vocab,
+                            net.max_pos, net.padding_idx)
+    else:
+        hip.layernorm_bwd(dt, dh, ctx["s0"], ctx["st0"], emb.LayerNorm.weight, ds0, None, A.g(emb.LayerNorm.weight), A.g(emb.LayerNorm.bias), M, Hd,
+                          drop_in=ctx["d0"], dcolsum=A.g(emb.token_type_embeddings.weight)[0])      # token_type_ids = 0: every row adds to row 0
+        hip.embed_bwd(dt, ctx["ids"], ds0, A.g(emb.word_embeddings.weight), A.g(emb.position_embeddings.weight), M, L, Hd, net.vocab,
+                      padding_idx=0)      # HF BertEmbeddings: nn.Embedding(vocab, hidden, padding_idx=pad_token_id = 0)
     if own_group is not None:
         own_group.launch()
         if staged:

@@ -226,9 +226,14 @@ __global__ __launch_bounds__(256) void embed_fwd_kernel(const int64_t* ids, cons
 constexpr int EMB_SEGS = 4, EMB_COLS = 16;      // C <= 128 * EMB_COLS
 DEV float ld1(const bf16* p) { return bf2f(*p); }
 DEV float ld1(const float* p) { return *p; }
-template <typename T>
+// MP (MPNet): the position row of a token is pids[row] (embed_mpnet_fwd_kernel) instead of l, so the position sums are run-merged like the word
+// sums — captions padded at the tail share pid = l + 2 at position l — and rows with pid == pos_pad add nothing (nn.Embedding(padding_idx)).
+// The operands come as a trailing argument that is empty for the BERT instantiation, whose code is therefore what it was without the variant.
+template <bool MP> struct EmbMp {};
+template <> struct EmbMp<true> { const int32_t* pids; int max_pos, pos_pad; };
+template <typename T, bool MP = false>
 __global__ __launch_bounds__(128) void embed_bwd_kernel(const int64_t* __restrict__ ids, const T* __restrict__ d, float* __restrict__ dword, float* __restrict__ dpos,
-                                                        int B, int L, int C, int vocab, int padding_idx) {
+                                                        int B, int L, int C, int vocab, int padding_idx, EmbMp<MP> mp) {
   // (position, segment) pairs are walked grid-stride: normally one per workgroup; the deterministic-reduction mode (det.h) launches a single
   // workgroup, whose threads own disjoint columns and add in program order
   for (int blk = blockIdx.x; blk < L * EMB_SEGS; blk += gridDim.x) {
@@ -251,33 +256,138 @@ __global__ __launch_bounds__(128) void embed_bwd_kernel(const int64_t* __restric
 #pragma unroll
     for (int j = 0; j < EMB_COLS; ++j) wacc[j] = 0.f;
   };
+  int pcur = -1;
+  auto pflush = [&]() {
+    if constexpr (MP) {
+      if (dpos && pcur >= 0 && pcur != mp.pos_pad) {
+#pragma unroll
+        for (int j = 0; j < EMB_COLS; ++j)
+          if (t + 128 * j < C) atomic_add_f32(dpos + (size_t)pcur * C + t + 128 * j, pacc[j]);
+      }
+#pragma unroll
+      for (int j = 0; j < EMB_COLS; ++j) pacc[j] = 0.f;
+    }
+  };
   // the next caption's row is fetched before this one's atomics are issued (the loop is otherwise one load latency per caption)
   float v[EMB_COLS], vn[EMB_COLS];
   int64_t id = 0, idn = 0;
-  auto fetch = [&](int b, float (&dst)[EMB_COLS], int64_t& di) {
+  int pid = 0, pidn = 0;
+  auto fetch = [&](int b, float (&dst)[EMB_COLS], int64_t& di, int& dp) {
     const size_t row = (size_t)b * L + l;
     di = ids[row];
+    if constexpr (MP) dp = mp.pids[row];
 #pragma unroll
     for (int j = 0; j < EMB_COLS; ++j) dst[j] = t + 128 * j < C ? ld1(d + row * C + t + 128 * j) : 0.f;
   };
-  if (b0 < b1) fetch(b0, vn, idn);
+  if (b0 < b1) fetch(b0, vn, idn, pidn);
   for (int b = b0; b < b1; ++b) {
     id = idn;
+    pid = pidn;
 #pragma unroll
     for (int j = 0; j < EMB_COLS; ++j) v[j] = vn[j];
-    if (b + 1 < b1) fetch(b + 1, vn, idn);
+    if (b + 1 < b1) fetch(b + 1, vn, idn, pidn);
     if (id < 0) id = 0;
     if (id >= vocab) id = vocab - 1;
     if (id != cur) { flush(); cur = id; }
+    if constexpr (MP) {
+      if (pid < 0) pid = 0;
+      if (pid >= mp.max_pos) pid = mp.max_pos - 1;
+      if (pid != pcur) { pflush(); pcur = pid; }
+    }
 #pragma unroll
     for (int j = 0; j < EMB_COLS; ++j) { pacc[j] += v[j]; wacc[j] += v[j]; }
   }
   flush();
-  if (dpos && b1 > b0) {
+  if constexpr (MP) {
+    pflush();
+  } else {
+    if (dpos && b1 > b0) {
 #pragma unroll
-    for (int j = 0; j < EMB_COLS; ++j)
-      if (t + 128 * j < C) atomic_add_f32(dpos + (size_t)l * C + t + 128 * j, pacc[j]);
+      for (int j = 0; j < EMB_COLS; ++j)
+        if (t + 128 * j < C) atomic_add_f32(dpos + (size_t)l * C + t + 128 * j, pacc[j]);
+    }
   }
+  }
+}
+
+// MPNet embeddings: out[row] = word[ids[row]] + pos[pid], pid = pad + (ids[row] != pad ? #{l' <= l : ids[b][l'] != pad} : 0)
+// (transformers create_position_ids_from_input_ids; no token types). One wave per row: lane l' < L holds the caption's l'-th id, an inclusive
+// prefix count over the lanes gives every row's pid without a host pass. pids (int32 [M]) is kept for the backward.
+template <typename T>
+__global__ __launch_bounds__(256) void embed_mpnet_fwd_kernel(const int64_t* ids, const T* word, const T* pos, T* out, int32_t* pids, int M, int L, int C,
+                                                              int vocab, int max_pos, int pad) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nchunk = C / 8;
+  for (int row = blockIdx.x * 4 + wave; row < M; row += gridDim.x * 4) {      // (wave-uniform: the shuffles below are wave-wide)
+    const int b = row / L, l = row % L;
+    const bool real = lane < L && ids[(size_t)b * L + lane] != pad;
+    const float flag = real ? 1.f : 0.f;
+    float cnt = flag;
+    for (int off = 1; off < 32; off <<= 1) {      // L <= 32
+      float up = wave_shfl(cnt, (lane - off) & 63);
+      if (lane >= off) cnt += up;
+    }
+    const float mine = wave_shfl(cnt, l), mreal = wave_shfl(flag, l);
+    int pid = pad + (mreal != 0.f ? (int)mine : 0);
+    if (pid < 0) pid = 0;
+    if (pid >= max_pos) pid = max_pos - 1;
+    int64_t id = ids[row];
+    if (id < 0) id = 0;
+    if (id >= vocab) id = vocab - 1;
+    if (lane == 0 && pids) pids[row] = pid;
+    for (int c = lane; c < nchunk; c += 64) {
+      float a[8], p[8];
+      load8(word + (size_t)id * C + c * 8, a);
+      load8(pos + (size_t)pid * C + c * 8, p);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) a[e] += p[e];
+      store8(out + (size_t)row * C + c * 8, a);
+    }
+  }
+}
+
+// Masked mean over the tokens (sentence-transformers mean pooling): out[b] = sum_l h[b][l] * mask[b][l] / max(sum_l mask[b][l], 1e-9);
+// inv[b] = 1 / that denominator, for the backward. A caption whose mask is all zero gives 0.
+template <typename T>
+__global__ __launch_bounds__(256) void mean_pool_fwd_kernel(const T* h, const int64_t* mask, T* out, float* inv, int B, int L, int C) {
+  const int nchunk = C / 8;
+  const size_t total = (size_t)B * nchunk;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int c = (int)(i % nchunk), b = (int)(i / nchunk);
+    float acc[8], cnt = 0.f;
+    zero8(acc);
+    for (int l = 0; l < L; ++l) {
+      const float m = (float)mask[(size_t)b * L + l];
+      cnt += m;
+      if (m != 0.f) {
+        float v[8];
+        load8(h + ((size_t)b * L + l) * C + c * 8, v);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] += v[e] * m;
+      }
+    }
+    const float den = fmaxf(cnt, 1e-9f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] /= den;
+    store8(out + (size_t)b * C + c * 8, acc);
+    if (c == 0) inv[b] = 1.0f / den;
+  }
+}
+// dh[b][l] = mask[b][l] * inv[b] * dy[b], for every token
+template <typename T>
+__global__ __launch_bounds__(256) void mean_pool_bwd_kernel(const T* dy, const int64_t* mask, const float* inv, T* dh, int B, int L, int C) {
+  const int nchunk = C / 8;
+  const size_t total = (size_t)B * L * nchunk;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int c = (int)(i % nchunk);
+    const size_t row = i / nchunk;
+    const int b = (int)(row / L);
+    const float s = (float)mask[row] * inv[b];
+    float v[8];
+    load8(dy + (size_t)b * C + c * 8, v);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] *= s;
+    store8(dh + row * C + c * 8, v);
   }
 }
 
@@ -316,7 +426,9 @@ DEV void attn_load_rows(const T* base, size_t row_stride, int L, float* dst, int
 }
 
 // scores + softmax for all rows: p[i][j] (un-dropped probabilities), i,j < 32 (rows/cols >= L are zero)
-DEV void attn_probs(AttnSmem& sm, const int64_t* mask_row, int L, int lane) {
+// BIAS (MPNet): bias_h = this head's [32][32] additive bias (relative_attention_bias), added after the 1/8 scale and before the mask
+template <bool BIAS>
+DEV void attn_probs(AttnSmem& sm, const int64_t* mask_row, int L, int lane, const float* bias_h) {
   const int j = lane & 31, half = lane >> 5;
   const bool jvalid = j < L;
   float madd = 0.f;
@@ -326,7 +438,8 @@ DEV void attn_probs(AttnSmem& sm, const int64_t* mask_row, int L, int lane) {
     float s = 0.f;
 #pragma unroll 16
     for (int d = 0; d < AT_D; ++d) s += sm.q[i * AT_PQ + d] * sm.k[j * AT_PQ + d];
-    s = s * 0.125f + madd;
+    if constexpr (BIAS) s = (s * 0.125f + bias_h[i * AT_L + j]) + madd;
+    else s = s * 0.125f + madd;
     if (!jvalid) s = -INFINITY;
     float mx = s;
 #pragma unroll
@@ -339,8 +452,16 @@ DEV void attn_probs(AttnSmem& sm, const int64_t* mask_row, int L, int lane) {
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(64) void attention_fwd_kernel(const T* qkv, const int64_t* mask, T* ctx, int B, int L, int H, Drop drop) {
+// The bias operands of the MPNet instantiations (bias [H][32][32]; backward: the 63-entry bucket table and the partials [B*H][32]) come as a
+// trailing argument that is empty without BIAS, so the BERT instantiations are compiled from the text they always were.
+template <bool BIAS> struct AttnBias {};
+template <> struct AttnBias<true> { const float* bias; const int32_t* btab; float* partials; };
+template <bool BIAS> DEV const float* attn_bias_head(const AttnBias<BIAS>& ab, int h) {
+  if constexpr (BIAS) return ab.bias + (size_t)h * AT_L * AT_L; else return nullptr;
+}
+
+template <typename T, bool BIAS = false>
+__global__ __launch_bounds__(64) void attention_fwd_kernel(const T* qkv, const int64_t* mask, T* ctx, int B, int L, int H, Drop drop, AttnBias<BIAS> ab) {
   seed_resolve(drop.seed, drop.site);
   __shared__ AttnSmem sm;
   const int lane = threadIdx.x;
@@ -351,7 +472,7 @@ __global__ __launch_bounds__(64) void attention_fwd_kernel(const T* qkv, const i
   attn_load_rows(base + H * AT_D, ld, L, sm.k, lane);
   attn_load_rows(base + 2 * H * AT_D, ld, L, sm.v, lane);
   __syncthreads();
-  attn_probs(sm, mask ? mask + (size_t)b * L : nullptr, L, lane);
+  attn_probs<BIAS>(sm, mask ? mask + (size_t)b * L : nullptr, L, lane, attn_bias_head(ab, h));
   attn_dropmask(sm, drop, b * H + h, lane);
   __syncthreads();
   for (int i = 0; i < L; ++i) {
@@ -361,14 +482,32 @@ __global__ __launch_bounds__(64) void attention_fwd_kernel(const T* qkv, const i
     if constexpr (sizeof(T) == 2) ctx[oi] = f2bf(o); else ctx[oi] = o;
   }
 }
-
 struct AttnBwdSmem {
   AttnSmem f;
   float dO[AT_L * AT_PQ], dS[AT_L * AT_PP];
 };
 
-template <typename T>
-__global__ __launch_bounds__(64) void attention_bwd_kernel(const T* qkv, const int64_t* mask, const T* dctx, T* dqkv, int B, int L, int H, Drop drop) {
+// Gradient of the relative-position bias, first stage: the 32 bucket sums of one (batch, head)'s f32 dS tile (LDS, [32][pitch]). Lane d < 63 sums
+// the diagonal j - i = d - 31 over i, j < L from the top down; lane k < 32 then adds the diagonals whose bucket (btab[d], the 63-entry table of
+// relative offsets -31 .. 31) is k, in ascending offset order. No atomics and a fixed order: the same bits on every run. out = NULL: no store.
+DEV void attn_bucket_sums(const float* dS, int pitch, int L, const int32_t* btab, float* out, int lane) {
+  const int off = lane - 31;
+  float diag = 0.f;
+  if (lane < 63) {
+    const int i0 = off < 0 ? -off : 0, i1 = off > 0 ? L - off : L;      // i in [i0, i1) <=> 0 <= i + off < L
+    for (int i = i0; i < i1; ++i) diag += dS[i * pitch + i + off];
+  }
+  float acc = 0.f;
+  for (int d = 0; d < 63; ++d) {
+    const float v = wave_shfl(diag, d);
+    if (btab[d] == lane) acc += v;
+  }
+  if (lane < 32 && out) out[lane] = acc;
+}
+
+template <typename T, bool BIAS = false>
+__global__ __launch_bounds__(64) void attention_bwd_kernel(const T* qkv, const int64_t* mask, const T* dctx, T* dqkv, int B, int L, int H, Drop drop,
+                                                           AttnBias<BIAS> ab) {
   seed_resolve(drop.seed, drop.site);
   __shared__ AttnBwdSmem sm;
   const int lane = threadIdx.x;
@@ -380,7 +519,7 @@ __global__ __launch_bounds__(64) void attention_bwd_kernel(const T* qkv, const i
   attn_load_rows(base + 2 * H * AT_D, ld, L, sm.f.v, lane);
   attn_load_rows(dctx + (size_t)b * L * ((size_t)H * AT_D) + h * AT_D, (size_t)H * AT_D, L, sm.dO, lane);
   __syncthreads();
-  attn_probs(sm.f, mask ? mask + (size_t)b * L : nullptr, L, lane);
+  attn_probs<BIAS>(sm.f, mask ? mask + (size_t)b * L : nullptr, L, lane, attn_bias_head(ab, h));
   attn_dropmask(sm.f, drop, b * H + h, lane);
   __syncthreads();
   const int j = lane & 31, half = lane >> 5;
@@ -398,6 +537,7 @@ __global__ __launch_bounds__(64) void attention_bwd_kernel(const T* qkv, const i
     sm.dS[i * AT_PP + j] = pij * (dp - t);
   }
   __syncthreads();
+  if constexpr (BIAS) attn_bucket_sums(sm.dS, AT_PP, L, ab.btab, ab.partials + (size_t)blockIdx.x * AT_L, lane);      // d bias = dS
   // lane = d.  dV[j][d] = sum_i Pd[i][j] dO[i][d];  dK[j][d] = sum_i dS[i][j] Q[i][d] / 8;  dQ[i][d] = sum_j dS[i][j] K[j][d] / 8
   T* obase = dqkv + (size_t)b * L * ld + h * AT_D;
   for (int r = 0; r < L; ++r) {
@@ -413,7 +553,6 @@ __global__ __launch_bounds__(64) void attention_bwd_kernel(const T* qkv, const i
     else { o[0] = dq; o[H * AT_D] = dk; o[2 * H * AT_D] = dv; }
   }
 }
-
 // ------------------------------------------------------------------------------------------------ attention on MFMA (bf16)
 // Same math as the VALU kernels above, on v_mfma_f32_32x32x16_bf16: one wave per (batch, head), the whole 32x32 score tile in
 // one accumulator. Forward keeps the KEY index in registers (S^T = K Q^T), so the softmax row reduction is over registers plus
@@ -483,7 +622,8 @@ DEV void am_store_T(bf16* base, size_t ld, int L, int d0, const f32x16& a, float
   }
 }
 
-__global__ __launch_bounds__(256) void attention_mfma_fwd_kernel(const bf16* qkv, const int64_t* mask, bf16* ctx, int B, int L, int H, Drop drop) {
+template <bool BIAS = false>
+__global__ __launch_bounds__(256) void attention_mfma_fwd_kernel(const bf16* qkv, const int64_t* mask, bf16* ctx, int B, int L, int H, Drop drop, AttnBias<BIAS> ab) {
   seed_resolve(drop.seed, drop.site);
   __shared__ __attribute__((aligned(16))) AmFwdSmem sm[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -506,7 +646,12 @@ __global__ __launch_bounds__(256) void attention_mfma_fwd_kernel(const bf16* qkv
   // softmax over j (registers x the two lane halves) for the query i = lane&31
   float mx = -INFINITY;
 #pragma unroll
-  for (int r = 0; r < 16; ++r) { acc[r] = acc[r] * 0.125f + S.madd[am_row(r, lane)]; mx = fmaxf(mx, acc[r]); }
+  for (int r = 0; r < 16; ++r) {
+    // (BIAS: key j = am_row(r, lane) runs over 4 consecutive floats per register group, query i = lane&31)
+    if constexpr (BIAS) acc[r] = (acc[r] * 0.125f + ab.bias[((size_t)h * AT_L + (lane & 31)) * AT_L + am_row(r, lane)]) + S.madd[am_row(r, lane)];
+    else acc[r] = acc[r] * 0.125f + S.madd[am_row(r, lane)];
+    mx = fmaxf(mx, acc[r]);
+  }
   mx = fmaxf(mx, wave_shfl_xor(mx, 32));
   float den = 0.f;
 #pragma unroll
@@ -533,8 +678,9 @@ __global__ __launch_bounds__(256) void attention_mfma_fwd_kernel(const bf16* qkv
     if (live) am_store_T(ctx + (size_t)b * L * ((size_t)H * 64) + h * 64, (size_t)H * 64, L, db * 32, o, 1.f, lane);
   }
 }
-
-__global__ __launch_bounds__(128) void attention_mfma_bwd_kernel(const bf16* qkv, const int64_t* mask, const bf16* dctx, bf16* dqkv, int B, int L, int H, Drop drop) {
+template <bool BIAS = false>
+__global__ __launch_bounds__(128) void attention_mfma_bwd_kernel(const bf16* qkv, const int64_t* mask, const bf16* dctx, bf16* dqkv, int B, int L, int H, Drop drop,
+                                                                 AttnBias<BIAS> ab) {
   seed_resolve(drop.seed, drop.site);
   __shared__ __attribute__((aligned(16))) AmBwdSmem sm[2];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -574,7 +720,9 @@ __global__ __launch_bounds__(128) void attention_mfma_bwd_kernel(const bf16* qkv
   f32x16 pd, ds;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {      // softmax over j = across the 32 lanes of a half, per register row i
-    float s = p[r] * 0.125f + madd;
+    float s;
+    if constexpr (BIAS) s = (p[r] * 0.125f + ab.bias[((size_t)h * AT_L + am_row(r, lane)) * AT_L + j]) + madd;
+    else s = p[r] * 0.125f + madd;
     float mx = s;
 #pragma unroll
     for (int m = 16; m >= 1; m >>= 1) mx = fmaxf(mx, wave_shfl_xor(mx, m));
@@ -593,6 +741,12 @@ __global__ __launch_bounds__(128) void attention_mfma_bwd_kernel(const bf16* qkv
     pd[r] = pr * mul;
     ds[r] = pr * (dpd - t);
   }
+  if constexpr (BIAS) {
+    // the f32 dS tile, before it is rounded to bf16 for the three products, over the dropout multipliers: every lane overwrites exactly the
+    // elements it read above, so no barrier is needed in front of the stores
+#pragma unroll
+    for (int r = 0; r < 16; ++r) S.m[am_row(r, lane) * 33 + j] = ds[r];
+  }
   // dS^T image for dQ: T[j][i] = dS[i][j]
 #pragma unroll
   for (int g = 0; g < 4; ++g) {
@@ -602,6 +756,7 @@ __global__ __launch_bounds__(128) void attention_mfma_bwd_kernel(const bf16* qkv
     *(u32x2*)(S.t + j * AM_PT + (8 * g + 4 * (lane >> 5)) * 2) = pk.u;
   }
   __syncthreads();
+  if constexpr (BIAS) attn_bucket_sums(S.m, 33, L, ab.btab, live ? ab.partials + (size_t)bh * AT_L : nullptr, lane);
   bf16* ob = dqkv + (size_t)b * L * ld + h * 64;
 #pragma unroll
   for (int db = 0; db < 2; ++db) {
@@ -619,6 +774,35 @@ __global__ __launch_bounds__(128) void attention_mfma_bwd_kernel(const bf16* qkv
       am_store_T(ob + H * 64, ld, L, db * 32, dk, 0.125f, lane);
       am_store_T(ob, ld, L, db * 32, dq, 0.125f, lane);
     }
+  }
+}
+// bias[h][i][j] = rel[btab[j - i + 31]][h] for i, j < L, 0 elsewhere in the [32][32] tile: MPNet's relative_attention_bias (Embedding(32, H), shared by
+// all layers, trained) expanded once per step into the operand of the attention kernels above
+__global__ __launch_bounds__(256) void attention_bias_build_kernel(const float* rel, const int32_t* btab, float* bias, int H, int L) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= H * AT_L * AT_L) return;
+  const int h = idx / (AT_L * AT_L), i = (idx / AT_L) % AT_L, j = idx % AT_L;
+  float v = 0.f;
+  if (i < L && j < L) {
+    int k = btab[j - i + AT_L - 1];
+    k = k < 0 ? 0 : (k > AT_L - 1 ? AT_L - 1 : k);
+    v = rel[k * H + h];
+  }
+  bias[idx] = v;
+}
+// Second stage of the bias gradient: drel[k][h] += sum_r partials[r][h][k] over the R = (layers x batch) rows the backward kernels wrote. One
+// workgroup per head: 32 row slices x 32 buckets, the slices' sums added in slice order by one thread per bucket (no atomics).
+__global__ __launch_bounds__(1024) void attention_bias_grad_reduce_kernel(const float* partials, float* drel, int R, int H) {
+  __shared__ float red[32][33];
+  const int h = blockIdx.x, k = threadIdx.x & 31, part = threadIdx.x >> 5;
+  float acc = 0.f;
+  for (int r = part; r < R; r += 32) acc += partials[((size_t)r * H + h) * AT_L + k];
+  red[part][k] = acc;
+  __syncthreads();
+  if (threadIdx.x < 32) {
+    float t = 0.f;
+    for (int q = 0; q < 32; ++q) t += red[q][k];
+    drel[k * H + h] += t;
   }
 }
 
@@ -725,8 +909,8 @@ extern "C" int clite_embed_bwd(int dtype, const int64_t* ids, const void* d, flo
   hipStream_t st = (hipStream_t)stream;
   const int egrid = clite::deterministic() ? 1 : L * EMB_SEGS;
   DISPATCH(dtype,
-           hipLaunchKernelGGL(embed_bwd_kernel<bf16>, dim3(egrid), dim3(128), 0, st, ids, (const bf16*)d, dword, dpos, M / L, L, C, vocab, padding_idx),
-           hipLaunchKernelGGL(embed_bwd_kernel<float>, dim3(egrid), dim3(128), 0, st, ids, (const float*)d, dword, dpos, M / L, L, C, vocab, padding_idx));
+           hipLaunchKernelGGL(embed_bwd_kernel<bf16>, dim3(egrid), dim3(128), 0, st, ids, (const bf16*)d, dword, dpos, M / L, L, C, vocab, padding_idx, EmbMp<false>{}),
+           hipLaunchKernelGGL(embed_bwd_kernel<float>, dim3(egrid), dim3(128), 0, st, ids, (const float*)d, dword, dpos, M / L, L, C, vocab, padding_idx, EmbMp<false>{}));
   return (int)hipGetLastError();
 }
 
@@ -736,8 +920,8 @@ extern "C" int clite_attention_fwd(int dtype, const void* qkv, const int64_t* ma
   Drop d{drop_p, drop_seed, drop_site};
   hipStream_t st = (hipStream_t)stream;
   DISPATCH(dtype,
-           hipLaunchKernelGGL(attention_mfma_fwd_kernel, dim3((B * H + 3) / 4), dim3(256), 0, st, (const bf16*)qkv, mask, (bf16*)ctx, B, L, H, d),
-           hipLaunchKernelGGL(attention_fwd_kernel<float>, dim3(B * H), dim3(64), 0, st, (const float*)qkv, mask, (float*)ctx, B, L, H, d));
+           hipLaunchKernelGGL(attention_mfma_fwd_kernel<false>, dim3((B * H + 3) / 4), dim3(256), 0, st, (const bf16*)qkv, mask, (bf16*)ctx, B, L, H, d, AttnBias<false>{}),
+           hipLaunchKernelGGL(attention_fwd_kernel<float>, dim3(B * H), dim3(64), 0, st, (const float*)qkv, mask, (float*)ctx, B, L, H, d, AttnBias<false>{}));
   return (int)hipGetLastError();
 }
 
@@ -747,8 +931,90 @@ extern "C" int clite_attention_bwd(int dtype, const void* qkv, const int64_t* ma
   Drop d{drop_p, drop_seed, drop_site};
   hipStream_t st = (hipStream_t)stream;
   DISPATCH(dtype,
-           hipLaunchKernelGGL(attention_mfma_bwd_kernel, dim3((B * H + 1) / 2), dim3(128), 0, st, (const bf16*)qkv, mask, (const bf16*)dctx, (bf16*)dqkv, B, L, H, d),
-           hipLaunchKernelGGL(attention_bwd_kernel<float>, dim3(B * H), dim3(64), 0, st, (const float*)qkv, mask, (const float*)dctx, (float*)dqkv, B, L, H, d));
+           hipLaunchKernelGGL(attention_mfma_bwd_kernel<false>, dim3((B * H + 1) / 2), dim3(128), 0, st, (const bf16*)qkv, mask, (const bf16*)dctx, (bf16*)dqkv, B, L, H, d, AttnBias<false>{}),
+           hipLaunchKernelGGL(attention_bwd_kernel<float>, dim3(B * H), dim3(64), 0, st, (const float*)qkv, mask, (const float*)dctx, (float*)dqkv, B, L, H, d, AttnBias<false>{}));
+  return (int)hipGetLastError();
+}
+
+extern "C" int clite_attention_bias_fwd(int dtype, const void* qkv, const int64_t* mask, const float* bias, void* ctx, int B, int L, int H,
+                                        float drop_p, uint64_t drop_seed, uint32_t drop_site, void* stream) {
+  if (B <= 0 || L <= 0 || L > AT_L || H <= 0 || !qkv || !ctx || !bias) return -1;
+  Drop d{drop_p, drop_seed, drop_site};
+  AttnBias<true> ab{bias, nullptr, nullptr};
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype,
+           hipLaunchKernelGGL(attention_mfma_fwd_kernel<true>, dim3((B * H + 3) / 4), dim3(256), 0, st, (const bf16*)qkv, mask, (bf16*)ctx, B, L, H, d, ab),
+           hipLaunchKernelGGL((attention_fwd_kernel<float, true>), dim3(B * H), dim3(64), 0, st, (const float*)qkv, mask, (float*)ctx, B, L, H, d, ab));
+  return (int)hipGetLastError();
+}
+
+extern "C" int clite_attention_bias_bwd(int dtype, const void* qkv, const int64_t* mask, const float* bias, const int32_t* bucket_table, const void* dctx,
+                                        void* dqkv, float* dbias_partials, int B, int L, int H, float drop_p, uint64_t drop_seed, uint32_t drop_site,
+                                        void* stream) {
+  if (B <= 0 || L <= 0 || L > AT_L || H <= 0 || !qkv || !dctx || !dqkv || !bias || !bucket_table || !dbias_partials) return -1;
+  Drop d{drop_p, drop_seed, drop_site};
+  AttnBias<true> ab{bias, bucket_table, dbias_partials};
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype,
+           hipLaunchKernelGGL(attention_mfma_bwd_kernel<true>, dim3((B * H + 1) / 2), dim3(128), 0, st, (const bf16*)qkv, mask, (const bf16*)dctx, (bf16*)dqkv, B, L, H, d, ab),
+           hipLaunchKernelGGL((attention_bwd_kernel<float, true>), dim3(B * H), dim3(64), 0, st, (const float*)qkv, mask, (const float*)dctx, (float*)dqkv, B, L, H, d, ab));
+  return (int)hipGetLastError();
+}
+
+extern "C" int clite_attention_bias_build(const float* rel_weight, const int32_t* bucket_table, float* bias, int H, int L, void* stream) {
+  if (H <= 0 || L <= 0 || L > AT_L || !rel_weight || !bucket_table || !bias) return -1;
+  hipLaunchKernelGGL(attention_bias_build_kernel, dim3((H * AT_L * AT_L + 255) / 256), dim3(256), 0, (hipStream_t)stream, rel_weight, bucket_table, bias, H, L);
+  return (int)hipGetLastError();
+}
+
+extern "C" int clite_attention_bias_grad_reduce(const float* partials, float* drel, int rows, int H, void* stream) {
+  if (rows <= 0 || H <= 0 || !partials || !drel) return -1;
+  hipLaunchKernelGGL(attention_bias_grad_reduce_kernel, dim3(H), dim3(1024), 0, (hipStream_t)stream, partials, drel, rows, H);
+  return (int)hipGetLastError();
+}
+
+extern "C" int clite_embed_mpnet_fwd(int dtype, const int64_t* ids, const void* word, const void* pos, void* out, int32_t* pids, int M, int L, int C,
+                                     int vocab, int max_pos, int padding_idx, void* stream) {
+  if (M <= 0 || L <= 0 || L > 32 || M % L || C % 8 || vocab <= 0 || max_pos <= 0 || !ids || !word || !pos || !out) return -1;
+  int grid = (M + 3) / 4;
+  if (grid > 4096) grid = 4096;
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype,
+           hipLaunchKernelGGL(embed_mpnet_fwd_kernel<bf16>, dim3(grid), dim3(256), 0, st, ids, (const bf16*)word, (const bf16*)pos, (bf16*)out, pids, M, L, C, vocab, max_pos, padding_idx),
+           hipLaunchKernelGGL(embed_mpnet_fwd_kernel<float>, dim3(grid), dim3(256), 0, st, ids, (const float*)word, (const float*)pos, (float*)out, pids, M, L, C, vocab, max_pos, padding_idx));
+  return (int)hipGetLastError();
+}
+
+extern "C" int clite_embed_mpnet_bwd(int dtype, const int64_t* ids, const int32_t* pids, const void* d, float* dword, float* dpos, int M, int L, int C,
+                                     int vocab, int max_pos, int padding_idx, void* stream) {
+  if (M <= 0 || L <= 0 || M % L || C % 8 || C > 128 * EMB_COLS || vocab <= 0 || max_pos <= 0 || !ids || !pids || !d) return -1;
+  if (!dword && !dpos) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  const int egrid = clite::deterministic() ? 1 : L * EMB_SEGS;
+  EmbMp<true> mp{pids, max_pos, padding_idx};
+  DISPATCH(dtype,
+           hipLaunchKernelGGL((embed_bwd_kernel<bf16, true>), dim3(egrid), dim3(128), 0, st, ids, (const bf16*)d, dword, dpos, M / L, L, C, vocab, padding_idx, mp),
+           hipLaunchKernelGGL((embed_bwd_kernel<float, true>), dim3(egrid), dim3(128), 0, st, ids, (const float*)d, dword, dpos, M / L, L, C, vocab, padding_idx, mp));
+  return (int)hipGetLastError();
+}
+
+extern "C" int clite_mean_pool_fwd(int dtype, const void* h, const int64_t* mask, void* out, float* inv, int B, int L, int C, void* stream) {
+  if (B <= 0 || L <= 0 || C <= 0 || C % 8 || !h || !mask || !out || !inv) return -1;
+  int grid = ew_grid((size_t)B * (C / 8));
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype,
+           hipLaunchKernelGGL(mean_pool_fwd_kernel<bf16>, dim3(grid), dim3(256), 0, st, (const bf16*)h, mask, (bf16*)out, inv, B, L, C),
+           hipLaunchKernelGGL(mean_pool_fwd_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)h, mask, (float*)out, inv, B, L, C));
+  return (int)hipGetLastError();
+}
+
+extern "C" int clite_mean_pool_bwd(int dtype, const void* dy, const int64_t* mask, const float* inv, void* dh, int B, int L, int C, void* stream) {
+  if (B <= 0 || L <= 0 || C <= 0 || C % 8 || !dy || !mask || !inv || !dh) return -1;
+  int grid = ew_grid((size_t)B * L * (C / 8));
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype,
+           hipLaunchKernelGGL(mean_pool_bwd_kernel<bf16>, dim3(grid), dim3(256), 0, st, (const bf16*)dy, mask, inv, (bf16*)dh, B, L, C),
+           hipLaunchKernelGGL(mean_pool_bwd_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)dy, mask, inv, (float*)dh, B, L, C));
   return (int)hipGetLastError();
 }
 

@@ -52,10 +52,22 @@ def normalize_caption(caption: str, max_caption_length: int = 30) -> str:
     return "".join(ch for ch in c if not unicodedata.combining(ch))
 
 
-def hash_tokenize(caption: str, max_len: int, vocab: int = 30522):
+def text_framing(model_name: str) -> str:
+    """Which tokenizer framing a text tower's name selects — the same test the reference applies to the name (encoder.py:165): "bert" in it
+    means BERT ([CLS] ... [SEP], pad id 0), anything else the MPNet tower (<s> ... </s>, pad id 1)."""
+    return "bert" if "bert" in (model_name or "bert") else "mpnet"
+
+
+MPNET_VOCAB_SIZE = 30527          # transformers.MPNetConfig().vocab_size
+
+
+def hash_tokenize(caption: str, max_len: int, vocab: int = 30522, framing: str = "bert"):
     """normalize_caption, then map every word to a stable id in [1000, vocab); [CLS]=101 ... [SEP]=102 (the HF tokenizer files the
-    reference loads, data/tokenizers.py, are not available offline)."""
+    reference loads, data/tokenizers.py, are not available offline). framing "mpnet": <s>=0 ... </s>=2 around word ids in
+    [4, MPNET_VOCAB_SIZE), so that the specials 0 .. 3 (<s>, <pad>, </s>, <unk>) never occur inside a caption."""
     words = re.sub(r"[^a-z0-9 ]", " ", normalize_caption(caption, max_len)).split()
+    if framing == "mpnet":
+        return [0] + [4 + int.from_bytes(hashlib.md5(w.encode()).digest()[:4], "little") % (MPNET_VOCAB_SIZE - 4) for w in words][: max_len - 2] + [2]
     ids = [101] + [1000 + int.from_bytes(hashlib.md5(w.encode()).digest()[:4], "little") % (vocab - 1000) for w in words][: max_len - 2] + [102]
     return ids
 
@@ -64,9 +76,14 @@ class WordPieceTokenizer:
     """BERT uncased WordPiece over a local vocab.txt: BertNormalizer (clean text, lower-case, strip accents, CJK spacing) ->
     BertPreTokenizer (whitespace + punctuation) -> greedy longest-match WordPiece ("##" continuation, [UNK] for unmatched words, words
     over 100 characters -> [UNK]) -> "[CLS] ... [SEP]" -> truncation to max_length INCLUDING the two specials — i.e. what the reference's
-    `BertTokenizer(caption, padding=False, truncation=True, max_length=L)` returns in `input_ids` (data/dataloader.py:196-202)."""
+    `BertTokenizer(caption, padding=False, truncation=True, max_length=L)` returns in `input_ids` (data/dataloader.py:196-202).
+    framing "mpnet": the same pipeline with transformers.MPNetTokenizer's specials, read from the user's vocab.txt: "<s> ... </s>", pad
+    "<pad>", and as the unknown token "[UNK]" where the vocabulary has it (the published MPNet vocabularies do, and it is MPNetTokenizer's
+    default), else "<unk>"."""
 
-    def __init__(self, vocab_path: str):
+    SPECIALS = {"bert": ("[PAD]", "[CLS]", "[SEP]"), "mpnet": ("<pad>", "<s>", "</s>")}
+
+    def __init__(self, vocab_path: str, framing: str = "bert"):
         from tokenizers import Tokenizer, models, normalizers, pre_tokenizers, processors
         if not os.path.isfile(vocab_path):
             raise FileNotFoundError(f"WordPiece vocabulary {vocab_path!r} not found (DATA.TOKENIZER_VOCAB)")
@@ -77,22 +94,25 @@ class WordPieceTokenizer:
                 tok = line.rstrip("\n")
                 if tok != "" and tok not in vocab:
                     vocab[tok] = i
-        for special in ("[PAD]", "[UNK]", "[CLS]", "[SEP]"):
+        self.framing = framing
+        pad, cls, sep = self.SPECIALS[framing]
+        unk = "[UNK]" if framing == "bert" or "[UNK]" in vocab else "<unk>"
+        for special in (pad, unk, cls, sep):
             if special not in vocab:
                 raise ValueError(f"{vocab_path}: vocabulary lacks {special}")
-        self.pad_token_id, self.cls_token_id, self.sep_token_id = vocab["[PAD]"], vocab["[CLS]"], vocab["[SEP]"]
+        self.pad_token_id, self.cls_token_id, self.sep_token_id, self.unk_token_id = vocab[pad], vocab[cls], vocab[sep], vocab[unk]
         self.vocab_size = max(vocab.values()) + 1
-        tk = Tokenizer(models.WordPiece(vocab, unk_token="[UNK]", max_input_chars_per_word=100))
+        tk = Tokenizer(models.WordPiece(vocab, unk_token=unk, max_input_chars_per_word=100))
         tk.normalizer = normalizers.BertNormalizer(clean_text=True, handle_chinese_chars=True, strip_accents=None, lowercase=True)
         tk.pre_tokenizer = pre_tokenizers.BertPreTokenizer()
-        tk.post_processor = processors.TemplateProcessing(single="[CLS] $A [SEP]", special_tokens=[("[CLS]", self.cls_token_id), ("[SEP]", self.sep_token_id)])
+        tk.post_processor = processors.TemplateProcessing(single=f"{cls} $A {sep}", special_tokens=[(cls, self.cls_token_id), (sep, self.sep_token_id)])
         self._tk = tk
 
     def __getstate__(self):          # picklable for DataLoader workers (the reference's tokenizers do the same, data/tokenizers.py:80-92)
-        return {"vocab_path": self.vocab_path}
+        return {"vocab_path": self.vocab_path, "framing": self.framing}
 
     def __setstate__(self, st):
-        self.__init__(st["vocab_path"])
+        self.__init__(st["vocab_path"], st.get("framing", "bert"))
 
     def __call__(self, caption: str, max_length: int):
         self._tk.enable_truncation(max_length=max_length)
@@ -256,9 +276,12 @@ class _CaptionDataset(Dataset):
 
     def __init__(self, mode: str, image_size: int, max_caption_length: int, length: int, seed: int = 0, tokenizer_vocab: str = "",
                  image_transform=DEFAULT_IMAGE_TRANSFORM, gpu_augment: bool = False, source_size: int = 256, visual_self_supervised: bool = False,
-                 textual_self_supervised: bool = False):
+                 textual_self_supervised: bool = False, text_model: str = "bert-base-uncased"):
         self.mode, self.image_size, self.max_len, self.length, self.seed = mode, image_size, max_caption_length, length, seed
-        self.tokenizer = WordPieceTokenizer(tokenizer_vocab) if tokenizer_vocab else None
+        # the text tower's name (MODEL.TEXTUAL.NETWORK_NAME) picks the framing and the pad id: BERT [CLS] ... [SEP] / 0, MPNet <s> ... </s> / 1
+        self.framing = text_framing(text_model)
+        self.tokenizer = WordPieceTokenizer(tokenizer_vocab, self.framing) if tokenizer_vocab else None
+        self.pad_token_id = self.tokenizer.pad_token_id if self.tokenizer is not None else (0 if self.framing == "bert" else 1)
         self.image_transform = tuple(image_transform)
         self.gpu_augment, self.visual_ssl, self.textual_ssl = bool(gpu_augment), bool(visual_self_supervised), bool(textual_self_supervised)
         self.textual_ssl = self.textual_ssl and mode != "sbert"          # (frozen caption encodings: there is no caption to re-tokenise)
@@ -270,7 +293,7 @@ class _CaptionDataset(Dataset):
     def tokenize(self, caption: str):
         if self.tokenizer is not None:            # the reference's order: NormalizeCaption, then the BERT tokenizer (data/dataloader.py:194-202)
             return self.tokenizer(normalize_caption(caption, self.max_len), self.max_len)
-        return hash_tokenize(caption, self.max_len)
+        return hash_tokenize(caption, self.max_len, framing=self.framing)
 
     def image_path(self, idx):
         return None
@@ -339,9 +362,11 @@ class _CaptionDataset(Dataset):
         return item
 
     @staticmethod
-    def _pad_captions(tokens):
+    def _pad_captions(tokens, pad_id=0):
+        """ids right-padded with the tokenizer's pad id; the attention mask is 0 at the pads. (The reference pads the MASK with pad_token_id too,
+        data/dataloader.py:218-236 — all ones for MPNet's pad id 1; the correct mask is emitted here, README "MPNet text encoder".)"""
         L = max(len(t) for t in tokens)
-        ids = torch.zeros(len(tokens), L, dtype=torch.long)             # pad_token_id = 0
+        ids = torch.full((len(tokens), L), int(pad_id), dtype=torch.long)
         mask = torch.zeros(len(tokens), L, dtype=torch.long)
         for r, t in enumerate(tokens):
             ids[r, :len(t)] = t
@@ -368,9 +393,9 @@ class _CaptionDataset(Dataset):
         if self.mode == "sbert":
             batch["caption_encodings"] = torch.stack([i["caption_encodings"] for i in items])
         else:
-            batch["input_ids"], batch["attention_mask"] = self._pad_captions([i["caption_tokens"] for i in items])
+            batch["input_ids"], batch["attention_mask"] = self._pad_captions([i["caption_tokens"] for i in items], self.pad_token_id)
             if "aug_caption_tokens" in items[0]:
-                batch["aug_input_ids"], batch["aug_attention_mask"] = self._pad_captions([i["aug_caption_tokens"] for i in items])
+                batch["aug_input_ids"], batch["aug_attention_mask"] = self._pad_captions([i["aug_caption_tokens"] for i in items], self.pad_token_id)
         return batch
 
 

@@ -165,24 +165,27 @@ def build_zero_shot_parser():
     return parser
 
 
-def tokenize_texts(texts, max_length, vocab=""):
-    """(input_ids, attention_mask) int64 [N][max_length] of every text, padded with 0 (padding="max_length", truncation=True: reference
-    zero_shot.py:104-110, retrieval.py:94-100). The project's WordPiece tokenizer when a vocabulary file is configured, else hash_tokenize."""
-    from .data import WordPieceTokenizer, hash_tokenize, normalize_caption
-    tok = WordPieceTokenizer(vocab) if vocab else None
-    ids = torch.zeros(len(texts), max_length, dtype=torch.long)
+def tokenize_texts(texts, max_length, vocab="", text_model="bert-base-uncased"):
+    """(input_ids, attention_mask) int64 [N][max_length] of every text, padded with the pad id of the text tower `text_model` names (0 for BERT,
+    1 for MPNet: data.text_framing) (padding="max_length", truncation=True: reference zero_shot.py:104-110, retrieval.py:94-100). The project's
+    WordPiece tokenizer when a vocabulary file is configured, else hash_tokenize."""
+    from .data import WordPieceTokenizer, hash_tokenize, normalize_caption, text_framing
+    framing = text_framing(text_model)
+    tok = WordPieceTokenizer(vocab, framing) if vocab else None
+    pad = tok.pad_token_id if tok is not None else (0 if framing == "bert" else 1)
+    ids = torch.full((len(texts), max_length), pad, dtype=torch.long)
     mask = torch.zeros(len(texts), max_length, dtype=torch.long)
     for i, text in enumerate(texts):
-        t = tok(normalize_caption(text, max_length), max_length) if tok is not None else hash_tokenize(text, max_length)
+        t = tok(normalize_caption(text, max_length), max_length) if tok is not None else hash_tokenize(text, max_length, framing=framing)
         t = list(t)[:max_length]
         ids[i, :len(t)] = torch.tensor(t, dtype=torch.long)
         mask[i, :len(t)] = 1
     return ids, mask
 
 
-def tokenize_prompts(names, template, max_length, vocab=""):
+def tokenize_prompts(names, template, max_length, vocab="", text_model="bert-base-uncased"):
     """(input_ids, attention_mask) int64 [C][max_length] of template.format(name) for every class (tokenize_texts)."""
-    return tokenize_texts([template.format(name.replace("_", " ")) for name in names], max_length, vocab)
+    return tokenize_texts([template.format(name.replace("_", " ")) for name in names], max_length, vocab, text_model)
 
 
 def zero_shot_main(_A):
@@ -202,7 +205,7 @@ def zero_shot_main(_A):
         ds = RandomLabelledDataset(image_size=size, length=500, split="val", seed=_C.RANDOM_SEED)
     else:
         ds = ImageFolderDataset(_A.data_root, "val", tuple(_C.DATA.IMAGE_TRANSFORM_VAL), size)
-    ids, mask = tokenize_prompts(ds.classes, _A.prompt, _A.max_length, _C.DATA.TOKENIZER_VOCAB)
+    ids, mask = tokenize_prompts(ds.classes, _A.prompt, _A.max_length, _C.DATA.TOKENIZER_VOCAB, _C.MODEL.TEXTUAL.NETWORK_NAME)
     text = retrieval.embed_texts(model, ids.to(device), mask.to(device), _A.batch_size)
     acc = torch.zeros(4, device=device)
     loader = DataLoader(ds, batch_size=_A.batch_size, shuffle=False, num_workers=_A.cpu_workers, collate_fn=ds.collate_fn)
@@ -381,7 +384,7 @@ def retrieval_main(_A):
     if _A.weight_init == "vlinfo":
         CheckpointManager(model=arch).load(_A.checkpoint_path)
     arch = arch.to(device)
-    ids, mask = tokenize_texts(dataset.text, 30, _C.DATA.TOKENIZER_VOCAB)
+    ids, mask = tokenize_texts(dataset.text, 30, _C.DATA.TOKENIZER_VOCAB, _C.MODEL.TEXTUAL.NETWORK_NAME)
     val_result = retrieval.evaluate(arch, loader, ids, mask)
     print(val_result)
     log_stats = {**{f"val_{k}": v for k, v in val_result.items()}}
@@ -414,7 +417,7 @@ def build_cluster_parser():
 
 
 @torch.no_grad()
-def embed_captions(model, captions, max_length, vocab="", batch_size=256):
+def embed_captions(model, captions, max_length, vocab="", batch_size=256, text_model="bert-base-uncased"):
     """f32 [N][768] on the model's device: the text encoder's features (eval mode, no projection head) of every caption through
     clite_l2_normalize. Stands in for the reference's paraphrase-mpnet-base-v2 sentence encoder (scripts/cluster.py:115-124), which does not
     exist offline."""
@@ -425,7 +428,7 @@ def embed_captions(model, captions, max_length, vocab="", batch_size=256):
     enc.eval()
     outs = []
     for i in range(0, len(captions), batch_size):
-        ids, mask = tokenize_texts(captions[i:i + batch_size], max_length, vocab)
+        ids, mask = tokenize_texts(captions[i:i + batch_size], max_length, vocab, text_model)
         f = enc({"input_ids": ids.to(device), "attention_mask": mask.to(device)}).contiguous()
         o = torch.empty_like(f)
         hip.l2_normalize(rt.dt, f, o, f.shape[0], f.shape[1])
@@ -478,7 +481,7 @@ def cluster_main(_A):
         if _A.weight_init == "vlinfo":
             CheckpointManager(model=arch).load(_A.checkpoint_path)
         arch = arch.to(device)
-        X = embed_captions(arch, captions, int(_C.DATA.MAX_CAPTION_LENGTH), _C.DATA.TOKENIZER_VOCAB, _A.batch_size)
+        X = embed_captions(arch, captions, int(_C.DATA.MAX_CAPTION_LENGTH), _C.DATA.TOKENIZER_VOCAB, _A.batch_size, _C.MODEL.TEXTUAL.NETWORK_NAME)
     X_host = X.cpu().numpy()
     _save_pickle({i: [captions[i]] for i in range(n)}, os.path.join(out_dir, f"img_id_caption_map_{split}.pkl"))
     _save_pickle({i: (dataset.image_path(i) or "") for i in range(n)}, os.path.join(out_dir, f"img_id_filename_map_{split}.pkl"))

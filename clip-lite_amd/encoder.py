@@ -131,8 +131,11 @@ class _TransformFn(torch.autograd.Function):
 
 class TextEncoder(nn.Module):
     r"""Reference encoder.py:122-205. Modes on the HIP path: ``"sbert"`` (frozen sentence embeddings passed through, 0 parameters)
-    and ``"train_sbert"`` with a *bert* ``model_name`` (random-init BertModel, ``pooler_output``). GloVe / MPNet / pretrained
-    downloads need assets or network that are unavailable and raise."""
+    and ``"train_sbert"`` with ``pretrained=False``: a ``model_name`` containing "bert" builds the random-init BertModel and returns
+    ``pooler_output``; any other name (the reference's "sentence-transformers/paraphrase-mpnet-base-v2") builds the random-init MPNetModel
+    (mpnet.py) and returns the masked mean over the token states (reference encoder.py:171-175, 197-198). One deviation on that branch:
+    the reference ignores ``num_hidden_layers`` there and always builds MPNetConfig()'s 12 layers; here it is honoured (default 12).
+    GloVe and pretrained weights need assets or a download that are unavailable and raise."""
 
     def __init__(self, word_dict=None, mode="train_sbert", transform_embedding=False, txt_enc_dim=512, glove_path=None, train_enc=False,
                  load_glove=True, model_name="bert-base-uncased", pretrained=False, num_hidden_layers=12):
@@ -145,10 +148,16 @@ class TextEncoder(nn.Module):
         if mode == "sbert":
             in_dim = 768
         elif mode == "train_sbert":
-            if pretrained or "bert" not in model_name:
-                raise RuntimeError("only a randomly initialised BERT text encoder can be built offline (no pretrained/MPNet download)")
-            print("Using bert model with layers: " + str(self.num_hidden_layers))
-            self.strans = BertModel(num_hidden_layers=self.num_hidden_layers)
+            if pretrained:
+                raise RuntimeError(f"pretrained weights of {model_name!r} are a download, which is not available; build the randomly initialised "
+                                   "encoder (MODEL.TEXTUAL.PRETRAINED false) and load a state_dict instead")
+            if "bert" in model_name:
+                print("Using bert model with layers: " + str(self.num_hidden_layers))
+                self.strans = BertModel(num_hidden_layers=self.num_hidden_layers)
+            else:
+                from .mpnet import MPNetModel
+                print("Using mpnet model with layers: " + str(self.num_hidden_layers))
+                self.strans = MPNetModel(num_hidden_layers=self.num_hidden_layers)
             in_dim = 768
         else:
             raise NotImplementedError(f"text encoder mode {mode!r} needs assets that are not available (GloVe vectors / HF hub)")
@@ -172,6 +181,8 @@ class TextEncoder(nn.Module):
     def train_enc(self):
         for param in self.strans.parameters():
             param.requires_grad = True
+        if hasattr(self.strans, "freeze_unused"):
+            self.strans.freeze_unused()          # MPNet's pooler never takes part in the step (mpnet.py)
 
     def dont_train_enc(self):
         for param in self.strans.parameters():

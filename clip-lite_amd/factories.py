@@ -40,7 +40,7 @@ class PretrainingDatasetFactory(Factory):
     def from_config(cls, config: Config, split: str = "train"):
         _C = config
         kwargs = {"mode": _C.MODEL.TEXTUAL.NAME, "image_size": _C.DATA.IMAGE_CROP_SIZE, "max_caption_length": _C.DATA.MAX_CAPTION_LENGTH,
-                  "tokenizer_vocab": _C.DATA.TOKENIZER_VOCAB,
+                  "tokenizer_vocab": _C.DATA.TOKENIZER_VOCAB, "text_model": _C.MODEL.TEXTUAL.NETWORK_NAME,
                   # transform names as configured; resize / crop transforms take IMAGE_CROP_SIZE (reference factories.py:213-224)
                   "image_transform": tuple(getattr(_C.DATA, f"IMAGE_TRANSFORM_{split.upper()}")),
                   "gpu_augment": _C.DATA.GPU_AUGMENT, "source_size": _C.DATA.GPU_AUGMENT_SOURCE_SIZE,

@@ -136,6 +136,14 @@ _SIGNATURES = {
     "clite_embed_bwd": [_I, _V, _V, _V, _V, _I, _I, _I, _I, _I, _V],
     "clite_attention_fwd": [_I, _V, _V, _V, _I, _I, _I, _F, _U64, _U32, _V],
     "clite_attention_bwd": [_I, _V, _V, _V, _V, _I, _I, _I, _F, _U64, _U32, _V],
+    "clite_attention_bias_fwd": [_I, _V, _V, _V, _V, _I, _I, _I, _F, _U64, _U32, _V],
+    "clite_attention_bias_bwd": [_I, _V, _V, _V, _V, _V, _V, _V, _I, _I, _I, _F, _U64, _U32, _V],
+    "clite_attention_bias_build": [_V, _V, _V, _I, _I, _V],
+    "clite_attention_bias_grad_reduce": [_V, _V, _I, _I, _V],
+    "clite_embed_mpnet_fwd": [_I, _V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _V],
+    "clite_embed_mpnet_bwd": [_I, _V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _V],
+    "clite_mean_pool_fwd": [_I, _V, _V, _V, _V, _I, _I, _I, _V],
+    "clite_mean_pool_bwd": [_I, _V, _V, _V, _V, _I, _I, _I, _V],
     "clite_tanh_bwd": [_I, _V, _V, _V, _U64, _V],
     "clite_critic_jsd_fwd": [_I, _V, _V, _V, _I, _I, _V, _V, _V, _V],
     "clite_l2_normalize": [_I, _V, _V, _I, _I, _V],
@@ -821,6 +829,69 @@ def attention_fwd(dt, qkv, mask, ctx, B, L, H, drop=NO_DROP):
 
 def attention_bwd(dt, qkv, mask, dctx, dqkv, B, L, H, drop=NO_DROP):
     check(lib().clite_attention_bwd(dt, p(qkv), p(mask), p(dctx), p(dqkv), B, L, H, drop[0], drop[1], drop[2], stream_ptr(qkv)), "attention_bwd")
+
+
+def relative_position_buckets(num_buckets=32, max_distance=128, span=31):
+    """MPNet's bucket of the relative offsets j - i = -span .. span (transformers MPNetEncoder.relative_position_bucket) as an int32 list of
+    2 * span + 1 entries: the host-computed table the bias kernels take. Integer arithmetic on the thresholds, so no float rounding decides a bucket:
+    with half = 16 and 8 exact buckets, a distance n >= 8 lands in 8 + floor(8 * log(n / 8) / log(16)) = 8 + floor(2 * log2(n / 8)), i.e. the largest
+    t with 2^t <= (n / 8)^2."""
+    half = num_buckets // 2
+    exact = half // 2
+    assert (num_buckets, max_distance) == (32, 128), "the closed form below is for MPNetConfig's defaults"
+    out = []
+    for rel in range(-span, span + 1):
+        n = -rel
+        ret = half if n < 0 else 0
+        n = abs(n)
+        if n < exact:
+            ret += n
+        else:
+            t = 0
+            while 2 ** (t + 1) * exact * exact <= n * n:
+                t += 1
+            ret += min(exact + t, half - 1)
+        out.append(ret)
+    return out
+
+
+def attention_bias_fwd(dt, qkv, mask, bias, ctx, B, L, H, drop=NO_DROP):
+    check(lib().clite_attention_bias_fwd(dt, p(qkv), p(mask), p(bias), p(ctx), B, L, H, drop[0], drop[1], drop[2], stream_ptr(qkv)), "attention_bias_fwd")
+
+
+def attention_bias_bwd(dt, qkv, mask, bias, table, dctx, dqkv, partials, B, L, H, drop=NO_DROP):
+    """partials: f32 [B*H][32], overwritten (clite_attention_bias_grad_reduce adds its sum over B into the bias table's gradient)."""
+    assert partials.dtype == torch.float32 and partials.numel() >= B * H * 32 and table.dtype == torch.int32 and table.numel() == 63
+    check(lib().clite_attention_bias_bwd(dt, p(qkv), p(mask), p(bias), p(table), p(dctx), p(dqkv), p(partials), B, L, H, drop[0], drop[1], drop[2],
+                                         stream_ptr(qkv)), "attention_bias_bwd")
+
+
+def attention_bias_build(rel_weight, table, bias, H, L):
+    """rel_weight f32 [32][H], table int32 [63] -> bias f32 [H][32][32]."""
+    assert rel_weight.dtype == torch.float32 and tuple(rel_weight.shape) == (32, H) and bias.dtype == torch.float32 and bias.numel() == H * 1024
+    assert table.dtype == torch.int32 and table.numel() == 63
+    check(lib().clite_attention_bias_build(p(rel_weight), p(table), p(bias), H, L, stream_ptr(bias)), "attention_bias_build")
+
+
+def attention_bias_grad_reduce(partials, drel, rows, H):
+    assert partials.numel() >= rows * H * 32 and drel.dtype == torch.float32 and drel.numel() == 32 * H
+    check(lib().clite_attention_bias_grad_reduce(p(partials), p(drel), rows, H, stream_ptr(partials)), "attention_bias_grad_reduce")
+
+
+def embed_mpnet_fwd(dt, ids, word, pos, out, pids, M, L, Cc, vocab, max_pos, padding_idx):
+    check(lib().clite_embed_mpnet_fwd(dt, p(ids), p(word), p(pos), p(out), p(pids), M, L, Cc, vocab, max_pos, padding_idx, stream_ptr(out)), "embed_mpnet_fwd")
+
+
+def embed_mpnet_bwd(dt, ids, pids, d, dword, dpos, M, L, Cc, vocab, max_pos, padding_idx):
+    check(lib().clite_embed_mpnet_bwd(dt, p(ids), p(pids), p(d), p(dword), p(dpos), M, L, Cc, vocab, max_pos, padding_idx, stream_ptr(d)), "embed_mpnet_bwd")
+
+
+def mean_pool_fwd(dt, h, mask, out, inv, B, L, Cc):
+    check(lib().clite_mean_pool_fwd(dt, p(h), p(mask), p(out), p(inv), B, L, Cc, stream_ptr(out)), "mean_pool_fwd")
+
+
+def mean_pool_bwd(dt, dy, mask, inv, dh, B, L, Cc):
+    check(lib().clite_mean_pool_bwd(dt, p(dy), p(mask), p(inv), p(dh), B, L, Cc, stream_ptr(dh)), "mean_pool_bwd")
 
 
 def tanh_bwd(dt, dy, y, out, n):

@@ -191,11 +191,18 @@ class TrainStep:
     # and every tensor that crosses a stream (features, their gradients) is kept referenced for the lifetime of the graphs.
     def _direct_ok(self):
         m = self.model
+        inert = self._inert_params()
         from .loss import GlobalDiscriminatorDot
         return (getattr(m, "mode", None) == "train_sbert" and not m.text_encoder.transform_embedding and m.training
                 and isinstance(m.loss.global_d, GlobalDiscriminatorDot)
                 and not getattr(m.image_encoder, "frozen", False)
-                and all(p.requires_grad for p in m.parameters()))
+                and all(p.requires_grad for p in m.parameters() if id(p) not in inert))
+
+    def _inert_params(self):
+        """Parameters that exist for checkpoint-key parity only and are frozen by construction (the MPNet tower's pooler, mpnet.py): they do not make
+        the model a partly frozen one for the per-phase capture."""
+        st = getattr(self.model.text_encoder, "strans", None)
+        return {id(p) for p in st.pooler.parameters()} if getattr(st, "kind", "bert") == "mpnet" else set()
 
     def _capture(self, batch):
         if not self._direct_ok() or any(k in batch for k in ("neg_input_ids", "aug_image", "aug_image_plan", "aug_input_ids")):
@@ -340,6 +347,8 @@ class TrainStep:
         # missing 2; reference train.py:174-178). One group per segment costs a little at one rank (grouping gains from size), hence only with an exchange.
         nts = int(getattr(self, "text_segments", 3 if self.exchange is not None else 1) or 1)
         nts = max(1, min(nts, len(m.text_encoder.strans.encoder.layer)))
+        if m.text_encoder.strans.kind != "bert":
+            nts = 1          # the MPNet tower's shared bias table is final only behind the first layer: its backward stays one segment
         tsegs = self._tsegs = [f"t{i}" for i in range(nts)]
         if nts > 1:
             ws.update({k: hip.WgradGroup.alloc_workspace(rt.device) for k in tsegs[1:]})
@@ -578,15 +587,20 @@ class TrainStep:
 
     _CAPTION_KEYS = ("input_ids", "attention_mask", "neg_input_ids", "neg_attention_mask", "aug_input_ids", "aug_attention_mask")
 
+    def _caption_fill(self, key):
+        """What a caption tensor is padded with: the text tower's pad id for the ids (0 for BERT, 1 for MPNet), 0 for the masks."""
+        st = getattr(getattr(self.model, "text_encoder", None), "strans", None)
+        return int(getattr(st, "padding_idx", 0)) if key.endswith("input_ids") else 0
+
     def _padded(self, batch):
-        """Caption tensors right-padded with zeros to `pad_to` columns (see __init__); other entries untouched."""
+        """Caption tensors right-padded (ids with the pad id, masks with zeros: _caption_fill) to `pad_to` columns (see __init__); other entries untouched."""
         if not self.pad_to:
             return batch
         out = dict(batch)
         for k in self._CAPTION_KEYS:
             v = batch.get(k)
             if torch.is_tensor(v) and v.dim() == 2 and v.shape[1] < self.pad_to:
-                w = torch.zeros(v.shape[0], self.pad_to, dtype=v.dtype, device=v.device)
+                w = torch.full((v.shape[0], self.pad_to), self._caption_fill(k), dtype=v.dtype, device=v.device)
                 w[:, :v.shape[1]] = v
                 out[k] = w
         return out
@@ -641,7 +655,7 @@ class TrainStep:
                     if dst.shape == v.shape:
                         dst.copy_(v, non_blocking=True)
                     else:                               # a batch whose longest caption is shorter than the captured length
-                        dst.zero_()
+                        dst.fill_(self._caption_fill(k))
                         dst[:, :v.shape[1]].copy_(v, non_blocking=True)
         with torch.cuda.stream(feed) if feed is not None else contextlib.nullcontext():
             self.inner.upload_hp(sync, alpha, max_norm=self.clip if self.clip and self.clip > 0 else 0.0)

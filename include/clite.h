@@ -459,6 +459,31 @@ int clite_attention_fwd(int dtype, const void* qkv, const int64_t* mask, void* c
 int clite_attention_bwd(int dtype, const void* qkv, const int64_t* mask, const void* dctx, void* dqkv, int B, int L, int H,
                         float drop_p, uint64_t drop_seed, uint32_t drop_site, void* stream);
 
+/* ---- MPNet (transformers.MPNetModel) variants of the kernels above; the entry points above are unchanged.
+ * Attention with the relative-position bias: bias f32 [H][32][32] (clite_attention_bias_build) is added to q k^T / 8 before the mask.
+ * The backward also writes dbias_partials f32 [B*H][32]: the sums of the (batch, head)'s f32 dS tile over the (i, j) of each bucket, with
+ * bucket_table int32 [63] = bucket of the relative offsets j - i = -31 .. 31 (host-computed, values 0 .. 31). No float atomics: bit-identical runs. */
+int clite_attention_bias_fwd(int dtype, const void* qkv, const int64_t* mask, const float* bias, void* ctx, int B, int L, int H,
+                             float drop_p, uint64_t drop_seed, uint32_t drop_site, void* stream);
+int clite_attention_bias_bwd(int dtype, const void* qkv, const int64_t* mask, const float* bias, const int32_t* bucket_table, const void* dctx,
+                             void* dqkv, float* dbias_partials, int B, int L, int H, float drop_p, uint64_t drop_seed, uint32_t drop_site,
+                             void* stream);
+/* bias[h][i][j] = rel_weight[bucket_table[j - i + 31]][h] for i, j < L (0 elsewhere); rel_weight f32 [32][H] */
+int clite_attention_bias_build(const float* rel_weight, const int32_t* bucket_table, float* bias, int H, int L, void* stream);
+/* drel[k][h] += sum_r partials[r][h][k], r < rows (= layers x B slices of clite_attention_bias_bwd's output); fixed summation order */
+int clite_attention_bias_grad_reduce(const float* partials, float* drel, int rows, int H, void* stream);
+/* MPNetEmbeddings sum: out[row] = word[ids[row]] + pos[pid], pid = padding_idx + (ids[row] != padding_idx ? number of ids != padding_idx among the
+ * caption's first l + 1 : 0), computed in the kernel (L <= 32); pids int32 [M] (may be NULL) receives pid for the backward */
+int clite_embed_mpnet_fwd(int dtype, const int64_t* ids, const void* word, const void* pos, void* out, int32_t* pids, int M, int L, int C,
+                          int vocab, int max_pos, int padding_idx, void* stream);
+/* dword[ids[row]] += d[row] for ids[row] != padding_idx; dpos[pids[row]] += d[row] for pids[row] != padding_idx. Either may be NULL. */
+int clite_embed_mpnet_bwd(int dtype, const int64_t* ids, const int32_t* pids, const void* d, float* dword, float* dpos, int M, int L, int C,
+                          int vocab, int max_pos, int padding_idx, void* stream);
+/* Masked mean over tokens: out[b] = sum_l h[b][l] mask[b][l] / max(sum_l mask[b][l], 1e-9), inv[b] = 1 / that denominator; h [B][L][C], C % 8 == 0.
+ * Backward: dh[b][l] = mask[b][l] inv[b] dy[b] for every token. */
+int clite_mean_pool_fwd(int dtype, const void* h, const int64_t* mask, void* out, float* inv, int B, int L, int C, void* stream);
+int clite_mean_pool_bwd(int dtype, const void* dy, const int64_t* mask, const float* inv, void* dh, int B, int L, int C, void* stream);
+
 /* BertPooler tanh backward: out = dy * (1 - y^2), n % 8 == 0 */
 int clite_tanh_bwd(int dtype, const void* dy, const void* y, void* out, uint64_t n, void* stream);
 
