@@ -12,7 +12,7 @@ SIMFLAGS   := -x c++ -std=c++20 -O1 -g -fPIC -pthread -Itests/wavesim -Iinclude 
 
 .PHONY: hip sim diag variant clean
 hip: $(LIBDIR)/libclite_hip.so
-# diagnostic build (tools/README.md): kernel-selection knobs from the environment + the round-1 register-staged engine; never loaded by the product
+# diagnostic build (tools/README.md): kernel-selection knobs from the environment; never loaded by the product
 diag: build/diag/libclite_hip_diag.so
 sim: tests/wavesim/_build/libclite_sim.so
 

@@ -147,13 +147,10 @@ def _linear_grads(rt, lin, dy, x, M, dw=None, db=None, bias_done=False, defer=No
         if db is not None:
             defer.call(lambda: hip.colsum(rt.dt, dy, db, M, N))
         return
-
-    def launch():
-        if dw is not None:
-            hip.gemm_tn(rt.dt, dy, x, N, K, M, hip.epilogue(dw, K, atomic=True, out_f32=True))
-        if db is not None:
-            hip.colsum(rt.dt, dy, db, M, N)
-    rt.aux_launch(launch, dy, x)       # off the dgrad chain: runtime.DeviceRuntime.aux_launch
+    if dw is not None:
+        hip.gemm_tn(rt.dt, dy, x, N, K, M, hip.epilogue(dw, K, atomic=True, out_f32=True))
+    if db is not None:
+        hip.colsum(rt.dt, dy, db, M, N)
 
 
 def bert_forward(rt, net, input_ids, attention_mask, step):
@@ -297,7 +294,7 @@ def bert_backward(rt, net, ctx, dpooled, defer=None, seg=None):
     lo_layer, hi_layer = (0, nl) if seg is None else segment_layers(nl, seg)
     first, last = seg is None or seg[0] == 0, seg is None or seg[0] == seg[1] - 1
     own_group = None
-    if seg is None and defer is None and rt.group_wgrad and not rt.overlap_wgrad and not rt._capturing:      # (a capture cannot allocate the pinned staging)
+    if seg is None and defer is None and rt.group_wgrad and not rt._capturing:      # (a capture cannot allocate the pinned staging)
         defer = own_group = hip.WgradGroup(rt.dt)          # uncaptured backward: grouped launch at the end of this call
     staged, pooler_done = own_group is not None and getattr(rt, "exchange", None) is not None, False
     A.ensure_transposed(capturing=rt._capturing)
@@ -405,5 +402,4 @@ def bert_backward(rt, net, ctx, dpooled, defer=None, seg=None):
         else:
             rt.grads_ready(net)
     else:
-        rt.join_aux()
         rt.grads_ready(emb)

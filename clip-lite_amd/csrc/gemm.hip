@@ -1,4 +1,4 @@
-// Host launchers (C ABI, include/clite.h) for the implicit-GEMM engine in igemm.h.
+// Host launchers (C ABI, include/clite.h) for the implicit-GEMM engine (igemm.h, igemm_dma.h).
 #include "igemm_dma.h"
 #include "wide_api.h"
 #include "det.h"
@@ -46,7 +46,7 @@ template <typename T> struct Cfg {
 };
 
 // Kernel-selection knobs. The product library has none: every choice below is a fixed function of the problem shape. A diagnostic build
-// (-DCLITE_DIAG=1, tools/README.md) reads them from the environment for A/B timing and also carries the round-1 register-staged engine.
+// (-DCLITE_DIAG=1, tools/README.md) reads them from the environment for A/B timing.
 #ifndef CLITE_DIAG
 #define CLITE_DIAG 0
 #endif
@@ -55,14 +55,12 @@ template <typename T> struct Cfg {
 #endif
 #if CLITE_DIAG
 int diag_env(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-bool use_dma() { static int v = -1; if (v < 0) v = diag_env("CLITE_IGEMM_LEGACY", 0) ? 0 : 1; return v == 1; }
 int stages_pref() { static int v = -1; if (v < 0) v = diag_env("CLITE_IGEMM_STAGES", 0); return v; }     // 3|4 forces a ring depth
 int g2_pref() { static int v = -1; if (v < 0) v = diag_env("CLITE_IGEMM_G2", 1); return v; }              // 0 off, 2 forces the two-K-group kernel
 int xcd_split_pref() { static int v = -1; if (v < 0) v = diag_env("CLITE_XCD_SPLIT", 1); return v; }
 int split_target_pref() { static int v = -1; if (v < 0) v = diag_env("CLITE_SPLIT_TARGET", 0); return v; }
 int splitk_ws_pref() { static int v = -1; if (v < 0) v = diag_env("CLITE_SPLITK_WS", 1); return v; }
 #else
-constexpr bool use_dma() { return true; }
 constexpr int stages_pref() { return 0; }
 constexpr int g2_pref() { return 1; }
 constexpr int xcd_split_pref() { return 1; }
@@ -70,36 +68,23 @@ constexpr int split_target_pref() { return 0; }
 constexpr int splitk_ws_pref() { return 1; }
 #endif
 // operands as gemm_wide.hip's 8-wave kernels take them (wide_api.h)
-template <typename T, int ROWS, int BK, bool D> WideOperand wide_op(const GatherKC<T, ROWS, BK, D>& l) {
+template <typename T, int ROWS, int BK, bool D> WideOperand wide_op(const DmaKC<T, ROWS, BK, D>& l) {
   WideOperand o{};
   o.kind = D ? WOP_KC_DGRAD : WOP_KC; o.ptr = l.ptr; o.bytes = l.bytes; o.g = l.g;
   return o;
 }
-template <typename T, int COLS, int BK> WideOperand wide_op(const StridedXC<T, COLS, BK>& l) {
+template <typename T, int COLS, int BK> WideOperand wide_op(const DmaXCStrided<T, COLS, BK>& l) {
   WideOperand o{};
   o.kind = WOP_XC_STRIDED; o.ptr = l.ptr; o.bytes = l.bytes; o.ld = l.ld; o.Cx = l.Cx; o.Ck = l.Ck; o.RS = l.RS;
   return o;
 }
-template <typename T, int COLS, int BK> WideOperand wide_op(const GatherXC<T, COLS, BK>& l) {
+template <typename T, int COLS, int BK> WideOperand wide_op(const DmaXCGather<T, COLS, BK>& l) {
   WideOperand o{};
   o.kind = WOP_XC_GATHER; o.ptr = l.ptr; o.bytes = l.bytes; o.g = l.g;
   return o;
 }
 template <class L> struct IsDgrad { static constexpr bool value = false; };
-template <typename T, int ROWS, int BK> struct IsDgrad<GatherKC<T, ROWS, BK, true>> { static constexpr bool value = true; };
-template <class L> struct ToDma;
-template <typename T, int ROWS, int BK, bool D> struct ToDma<GatherKC<T, ROWS, BK, D>> {
-  typedef DmaKC<T, ROWS, BK, D> type;
-  static type make(const GatherKC<T, ROWS, BK, D>& l) { return type{l.ptr, l.bytes, l.g}; }
-};
-template <typename T, int COLS, int BK> struct ToDma<StridedXC<T, COLS, BK>> {
-  typedef DmaXCStrided<T, COLS, BK> type;
-  static type make(const StridedXC<T, COLS, BK>& l) { return type{l.ptr, l.bytes, l.ld, l.Cx, l.Ck, l.RS}; }
-};
-template <typename T, int COLS, int BK> struct ToDma<GatherXC<T, COLS, BK>> {
-  typedef DmaXCGather<T, COLS, BK> type;
-  static type make(const GatherXC<T, COLS, BK>& l) { return type{l.ptr, l.bytes, l.g}; }
-};
+template <typename T, int ROWS, int BK> struct IsDgrad<DmaKC<T, ROWS, BK, true>> { static constexpr bool value = true; };
 
 // ---- deterministic-reduction mode (det.h): column statistics of a GEMM output, from the stored tensor ---------------------------
 // Same quantities as the fused epilogues accumulate (sum v, sum v^2 of the stored values; or sum v, sum v*(bn_y - mean) when bn_y is set),
@@ -182,10 +167,8 @@ int launch(const LA& la, const LB& lb, const clite_epilogue& ep, int M, int N, i
   }
   if constexpr (sizeof(T) == 2 && std::is_same<CFG, typename Cfg<T>::C128>::value) {
     // bf16, 128-column-or-wider outputs: the wide-K 8-wave kernels (igemm_wide.h) where the shape allows
-    if (use_dma()) {
-      const int rcw = launch_wide(wide_op(la), wide_op(lb), ep, rm, M, N, Ktot, splits, st);
-      if (rcw != WIDE_NOT_TAKEN) return rcw;
-    }
+    const int rcw = launch_wide(wide_op(la), wide_op(lb), ep, rm, M, N, Ktot, splits, st);
+    if (rcw != WIDE_NOT_TAKEN) return rcw;
   }
   int ktiles = (Ktot + CFG::BK - 1) / CFG::BK;
   if (splits < 1) splits = 1;
@@ -194,121 +177,112 @@ int launch(const LA& la, const LB& lb, const clite_epilogue& ep, int M, int N, i
   splits = (ktiles + per - 1) / per;
   int tiles = ((M + CFG::BM - 1) / CFG::BM) * ((N + CFG::BN - 1) / CFG::BN);
   // >= 8 K splits: 1-D grid in which each XCD owns whole splits (igemm_dma.h)
-  const int xsplits = (xcd_split_pref() && splits >= 8 && use_dma()) ? splits : 0;
+  const int xsplits = (xcd_split_pref() && splits >= 8) ? splits : 0;
   const dim3 grid = xsplits ? dim3(8 * ((splits + 7) / 8) * tiles, 1, 1) : dim3(tiles, 1, splits);
-  if (use_dma()) {
-    typedef typename ToDma<LA>::type DA;
-    typedef typename ToDma<LB>::type DB;
-    // a grid that gives each CU at most ~2 workgroups hides DMA latency with a deeper ring instead (4 stages x 16 KB = 64 KB)
-    constexpr int STAGE = DA::BYTES + DB::BYTES;
-    if (ep.bn_y || ep.mask_after_residual) {     // BatchNorm-backward epilogue: its own (register-heavier) instantiation, dgrad loaders only
-      // it implements exactly: out = [(alpha*acc) (* relu'(aux))] (+ residual) [(* relu'(aux))], colsum; nothing else
-      if (ep.atomic || ep.act || ep.preact || ep.drop_p > 0.f || (ep.dact_aux && ep.dact != 1) || (ep.dact_aux && ep.relu_bits) || splits != 1) return -1;
-      if constexpr (IsDgrad<LA>::value) {
-        // the two forms of the bf16 ResNet backward get their own instantiations (igemm_epilogue_bn's FORM); everything else the run-time form
-        constexpr bool kc_b = !LB::XC;
-        int form = 0;
-        if (sizeof(T) == 2 && kc_b && ep.relu_bits && ep.bn_y && !ep.dact_aux && !ep.out_f32 && ep.alpha == 1.f) {
-          if (!ep.residual && !ep.mask_after_residual) form = ep.bias ? 5 : 1;
-          else if (ep.residual && ep.mask_after_residual) form = rm.on == 2 ? 3 : 2;
-        }
-        // row-range persistent form (igemm_dma_bn_kernel) for the short-K (1 x 1) dgrads whose tile count exceeds the resident slots — two
-        // workgroups per CU, three for the specialised forms on the 128 x 128 tile (half-tile staging: 48 KB of LDS, 168 registers); one
-        // tile per workgroup otherwise
-        const int slots = (CLITE_BN_HALF && form && CFG::BM == 128) ? CLITE_BN_SLOTS * 3 / 2 : CLITE_BN_SLOTS;
-        const int tiles_n = (N + CFG::BN - 1) / CFG::BN, tiles_m = (M + CFG::BM - 1) / CFG::BM;
-        int rows_per_wg = CFG::BM, slices = tiles_m;
-        if ((la.g.R * la.g.S == 1 || la.g.concat) && (long)tiles_m * tiles_n > slots && tiles_n <= slots && !deterministic()) {
-          slices = slots / tiles_n;
-          rows_per_wg = ((M + slices - 1) / slices + 7) & ~7;
-          if (rows_per_wg < CFG::BM) rows_per_wg = CFG::BM;
-          slices = (M + rows_per_wg - 1) / rows_per_wg;
-        }
-        const dim3 g(slices * tiles_n);
-        if constexpr (sizeof(T) == 2 && kc_b) {
-          if (form == 1) hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, DA, DB, 1>), g, dim3(256), 0, st, ToDma<LA>::make(la), ToDma<LB>::make(lb), ep, rm, M, N, ktiles, rows_per_wg, nullptr, nullptr);
-          else if (form == 2) hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, DA, DB, 2>), g, dim3(256), 0, st, ToDma<LA>::make(la), ToDma<LB>::make(lb), ep, rm, M, N, ktiles, rows_per_wg, nullptr, nullptr);
-          else if (form == 3) hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, DA, DB, 3>), g, dim3(256), 0, st, ToDma<LA>::make(la), ToDma<LB>::make(lb), ep, rm, M, N, ktiles, rows_per_wg, nullptr, nullptr);
-          else if (form == 5) hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, DA, DB, 5>), g, dim3(256), 0, st, ToDma<LA>::make(la), ToDma<LB>::make(lb), ep, rm, M, N, ktiles, rows_per_wg, nullptr, nullptr);
-          else hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, DA, DB, 0>), g, dim3(256), 0, st, ToDma<LA>::make(la), ToDma<LB>::make(lb), ep, rm, M, N, ktiles, rows_per_wg, nullptr, nullptr);
-        } else {
-          bool done = false;
-          if constexpr (sizeof(T) == 4) {
-            if (f32_split()) {
-              hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, DA, DB, 0, true>), g, dim3(256), 0, st, ToDma<LA>::make(la), ToDma<LB>::make(lb), ep, rm, M, N, ktiles, rows_per_wg, nullptr, nullptr);
-              done = true;
-            }
-          }
-          if (!done)
-            hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, DA, DB, 0>), g, dim3(256), 0, st, ToDma<LA>::make(la), ToDma<LB>::make(lb), ep, rm, M, N, ktiles, rows_per_wg, nullptr, nullptr);
-        }
-        return (int)hipGetLastError();
-      } else {
-        return -1;
+  // a grid that gives each CU at most ~2 workgroups hides DMA latency with a deeper ring instead (4 stages x 16 KB = 64 KB)
+  constexpr int STAGE = LA::BYTES + LB::BYTES;
+  if (ep.bn_y || ep.mask_after_residual) {     // BatchNorm-backward epilogue: its own (register-heavier) instantiation, dgrad loaders only
+    // it implements exactly: out = [(alpha*acc) (* relu'(aux))] (+ residual) [(* relu'(aux))], colsum; nothing else
+    if (ep.atomic || ep.act || ep.preact || ep.drop_p > 0.f || (ep.dact_aux && ep.dact != 1) || (ep.dact_aux && ep.relu_bits) || splits != 1) return -1;
+    if constexpr (IsDgrad<LA>::value) {
+      // the two forms of the bf16 ResNet backward get their own instantiations (igemm_epilogue_bn's FORM); everything else the run-time form
+      constexpr bool kc_b = !LB::XC;
+      int form = 0;
+      if (sizeof(T) == 2 && kc_b && ep.relu_bits && ep.bn_y && !ep.dact_aux && !ep.out_f32 && ep.alpha == 1.f) {
+        if (!ep.residual && !ep.mask_after_residual) form = ep.bias ? 5 : 1;
+        else if (ep.residual && ep.mask_after_residual) form = rm.on == 2 ? 3 : 2;
       }
-    }
-    // The HBM-bound 1 x 1 FORWARD convolutions of the 56 x 56 / 28 x 28 stages (K <= 512, thousands of tiles, plain bf16 store + column statistics:
-    // 3.4 - 3.8 TB/s as one tile per workgroup) in the row-range persistent structure of the BatchNorm-backward dgrads, which
-    // sustains 5.2 TB/s on the same tensors (igemm_epilogue_bn FORM 4: no operands, sums of v and v^2): every workgroup is resident at once, walks
-    // its own row range of one column tile and adds its column sums once.
-#ifndef CLITE_NO_PERSIST_FWD
-    if constexpr (sizeof(T) == 2 && !LA::XC && !LB::XC && !IsDgrad<LA>::value) {
-      const bool plain_fwd = !ep.atomic && !ep.out_f32 && !ep.preact && ep.act == CLITE_ACT_NONE && !ep.dact_aux && ep.drop_p <= 0.f && !ep.residual && !ep.bias &&
-                             ep.alpha == 1.f && !ep.relu_bits && !ep.splitk_ws && splits == 1 && rm.on == 0;
+      // row-range persistent form (igemm_dma_bn_kernel) for the short-K (1 x 1) dgrads whose tile count exceeds the resident slots (two
+      // workgroups per CU); one tile per workgroup otherwise
+      const int slots = CLITE_BN_SLOTS;
       const int tiles_n = (N + CFG::BN - 1) / CFG::BN, tiles_m = (M + CFG::BM - 1) / CFG::BM;
-      if (plain_fwd && la.g.R * la.g.S == 1 && ktiles <= 16 && (long)tiles_m * tiles_n > 2 * CLITE_BN_SLOTS && tiles_n <= CLITE_BN_SLOTS && !deterministic() &&
-          tile_policy_value() == 0) {
-        int slices = CLITE_BN_SLOTS / tiles_n;
-        int rows_per_wg = ((M + slices - 1) / slices + 7) & ~7;
+      int rows_per_wg = CFG::BM, slices = tiles_m;
+      if ((la.g.R * la.g.S == 1 || la.g.concat) && (long)tiles_m * tiles_n > slots && tiles_n <= slots && !deterministic()) {
+        slices = slots / tiles_n;
+        rows_per_wg = ((M + slices - 1) / slices + 7) & ~7;
         if (rows_per_wg < CFG::BM) rows_per_wg = CFG::BM;
         slices = (M + rows_per_wg - 1) / rows_per_wg;
-#ifdef CLITE_PROBE_AFRAG
-        if (g_probe_aff[0] && ktiles * CFG::BK <= 512) {
-          hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, DA, DB, 4, false, false, true>), dim3(slices * tiles_n), dim3(256), 0, st, ToDma<LA>::make(la), ToDma<LB>::make(lb), ep,
-                             rm, M, N, ktiles, rows_per_wg, g_probe_aff[0], g_probe_aff[1]);
-          return (int)hipGetLastError();
+      }
+      const dim3 g(slices * tiles_n);
+      if constexpr (sizeof(T) == 2 && kc_b) {
+        if (form == 1) hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, LA, LB, 1>), g, dim3(256), 0, st, la, lb, ep, rm, M, N, ktiles, rows_per_wg, nullptr, nullptr);
+        else if (form == 2) hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, LA, LB, 2>), g, dim3(256), 0, st, la, lb, ep, rm, M, N, ktiles, rows_per_wg, nullptr, nullptr);
+        else if (form == 3) hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, LA, LB, 3>), g, dim3(256), 0, st, la, lb, ep, rm, M, N, ktiles, rows_per_wg, nullptr, nullptr);
+        else if (form == 5) hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, LA, LB, 5>), g, dim3(256), 0, st, la, lb, ep, rm, M, N, ktiles, rows_per_wg, nullptr, nullptr);
+        else hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, LA, LB, 0>), g, dim3(256), 0, st, la, lb, ep, rm, M, N, ktiles, rows_per_wg, nullptr, nullptr);
+      } else {
+        bool done = false;
+        if constexpr (sizeof(T) == 4) {
+          if (f32_split()) {
+            hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, LA, LB, 0, true>), g, dim3(256), 0, st, la, lb, ep, rm, M, N, ktiles, rows_per_wg, nullptr, nullptr);
+            done = true;
+          }
         }
-#endif
-        hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, DA, DB, 4>), dim3(slices * tiles_n), dim3(256), 0, st, ToDma<LA>::make(la), ToDma<LB>::make(lb), ep, rm, M, N, ktiles,
-                           rows_per_wg, nullptr, nullptr);
+        if (!done)
+          hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, LA, LB, 0>), g, dim3(256), 0, st, la, lb, ep, rm, M, N, ktiles, rows_per_wg, nullptr, nullptr);
+      }
+      return (int)hipGetLastError();
+    } else {
+      return -1;
+    }
+  }
+  // The HBM-bound 1 x 1 FORWARD convolutions of the 56 x 56 / 28 x 28 stages (K <= 512, thousands of tiles, plain bf16 store + column statistics:
+  // 3.4 - 3.8 TB/s as one tile per workgroup) in the row-range persistent structure of the BatchNorm-backward dgrads, which
+  // sustains 5.2 TB/s on the same tensors (igemm_epilogue_bn FORM 4: no operands, sums of v and v^2): every workgroup is resident at once, walks
+  // its own row range of one column tile and adds its column sums once.
+#ifndef CLITE_NO_PERSIST_FWD
+  if constexpr (sizeof(T) == 2 && !LA::XC && !LB::XC && !IsDgrad<LA>::value) {
+    const bool plain_fwd = !ep.atomic && !ep.out_f32 && !ep.preact && ep.act == CLITE_ACT_NONE && !ep.dact_aux && ep.drop_p <= 0.f && !ep.residual && !ep.bias &&
+                           ep.alpha == 1.f && !ep.relu_bits && !ep.splitk_ws && splits == 1 && rm.on == 0;
+    const int tiles_n = (N + CFG::BN - 1) / CFG::BN, tiles_m = (M + CFG::BM - 1) / CFG::BM;
+    if (plain_fwd && la.g.R * la.g.S == 1 && ktiles <= 16 && (long)tiles_m * tiles_n > 2 * CLITE_BN_SLOTS && tiles_n <= CLITE_BN_SLOTS && !deterministic() &&
+        tile_policy_value() == 0) {
+      int slices = CLITE_BN_SLOTS / tiles_n;
+      int rows_per_wg = ((M + slices - 1) / slices + 7) & ~7;
+      if (rows_per_wg < CFG::BM) rows_per_wg = CFG::BM;
+      slices = (M + rows_per_wg - 1) / rows_per_wg;
+#ifdef CLITE_PROBE_AFRAG
+      if (g_probe_aff[0] && ktiles * CFG::BK <= 512) {
+        hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, LA, LB, 4, false, false, true>), dim3(slices * tiles_n), dim3(256), 0, st, la, lb, ep,
+                           rm, M, N, ktiles, rows_per_wg, g_probe_aff[0], g_probe_aff[1]);
         return (int)hipGetLastError();
       }
-    }
 #endif
-    // at most one workgroup per CU: two K-groups per workgroup (8 waves, in-workgroup split-K) instead of one wave per SIMD. bf16 only:
-    // the exact-f32 parity mode keeps one k-ordered fmaf chain per output, which is what tracks the CPU reference most closely
-    if (g2_pref() != 0 && 6 * STAGE <= 160 * 1024 && (((long)tiles * splits <= 256 && per >= 8 && sizeof(T) == 2) || g2_pref() == 2)) {
-      // (4- and 5-stage rings for this kernel were measured and dropped: 38.6 / 39.6 / 42.6 us on the N = 768 BERT shapes)
-      hipLaunchKernelGGL((igemm_dma_kernel_g2<T, CFG, DA, DB, 3>), grid, dim3(512), 0, st, ToDma<LA>::make(la), ToDma<LB>::make(lb), ep, rm,
-                         M, N, ktiles, per, xsplits);
+      hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, LA, LB, 4>), dim3(slices * tiles_n), dim3(256), 0, st, la, lb, ep, rm, M, N, ktiles,
+                         rows_per_wg, nullptr, nullptr);
       return (int)hipGetLastError();
     }
-    if constexpr (sizeof(T) == 4) {
-      if (f32_split()) {          // f32 storage, three bf16 MFMAs per product (clite_set_f32_split)
-        if (4 * STAGE <= 65536 && (long)tiles * splits <= 2 * 256 && per >= 4)
-          hipLaunchKernelGGL((igemm_dma_kernel<T, CFG, DA, DB, 4, 0, true>), grid, dim3(256), 0, st, ToDma<LA>::make(la), ToDma<LB>::make(lb), ep, rm, M, N, ktiles, per, xsplits);
-        else
-          hipLaunchKernelGGL((igemm_dma_kernel<T, CFG, DA, DB, 3, 0, true>), grid, dim3(256), 0, st, ToDma<LA>::make(la), ToDma<LB>::make(lb), ep, rm, M, N, ktiles, per, xsplits);
-        return (int)hipGetLastError();
-      }
-    }
-    bool deep = 4 * STAGE <= 65536 && (long)tiles * splits <= 2 * 256 && per >= 4 && stages_pref() != 3;
-    if (deep || (stages_pref() == 4 && 4 * STAGE <= 65536))
-      hipLaunchKernelGGL((igemm_dma_kernel<T, CFG, DA, DB, 4>), grid, dim3(256), 0, st, ToDma<LA>::make(la), ToDma<LB>::make(lb), ep, rm,
-                         M, N, ktiles, per, xsplits);
-    else if (sizeof(T) == 2 && !ep.atomic && !ep.out_f32 && !ep.preact && ep.act == CLITE_ACT_NONE && !ep.dact_aux && ep.drop_p <= 0.f && !ep.residual && !ep.bn_y &&
-             !ep.mask_after_residual)
-      // plain bf16 store (+ bias, + column statistics): the branch-free epilogue instantiation
-      hipLaunchKernelGGL((igemm_dma_kernel<T, CFG, DA, DB, 3, 2>), grid, dim3(256), 0, st, ToDma<LA>::make(la), ToDma<LB>::make(lb), ep, rm,
-                         M, N, ktiles, per, xsplits);
-    else
-      hipLaunchKernelGGL((igemm_dma_kernel<T, CFG, DA, DB, 3>), grid, dim3(256), 0, st, ToDma<LA>::make(la), ToDma<LB>::make(lb), ep, rm,
-                         M, N, ktiles, per, xsplits);
-  } else {
-#if CLITE_DIAG
-    hipLaunchKernelGGL((igemm_kernel<T, CFG, LA, LB>), dim3(tiles, 1, splits), dim3(256), 0, st, la, lb, ep, rm, M, N, ktiles, per);
-#endif
   }
+#endif
+  // at most one workgroup per CU: two K-groups per workgroup (8 waves, in-workgroup split-K) instead of one wave per SIMD. bf16 only:
+  // the exact-f32 parity mode keeps one k-ordered fmaf chain per output, which is what tracks the CPU reference most closely
+  if (g2_pref() != 0 && 6 * STAGE <= 160 * 1024 && (((long)tiles * splits <= 256 && per >= 8 && sizeof(T) == 2) || g2_pref() == 2)) {
+    // (4- and 5-stage rings for this kernel were measured and dropped: 38.6 / 39.6 / 42.6 us on the N = 768 BERT shapes)
+    hipLaunchKernelGGL((igemm_dma_kernel_g2<T, CFG, LA, LB, 3>), grid, dim3(512), 0, st, la, lb, ep, rm,
+                       M, N, ktiles, per, xsplits);
+    return (int)hipGetLastError();
+  }
+  if constexpr (sizeof(T) == 4) {
+    if (f32_split()) {          // f32 storage, three bf16 MFMAs per product (clite_set_f32_split)
+      if (4 * STAGE <= 65536 && (long)tiles * splits <= 2 * 256 && per >= 4)
+        hipLaunchKernelGGL((igemm_dma_kernel<T, CFG, LA, LB, 4, 0, true>), grid, dim3(256), 0, st, la, lb, ep, rm, M, N, ktiles, per, xsplits);
+      else
+        hipLaunchKernelGGL((igemm_dma_kernel<T, CFG, LA, LB, 3, 0, true>), grid, dim3(256), 0, st, la, lb, ep, rm, M, N, ktiles, per, xsplits);
+      return (int)hipGetLastError();
+    }
+  }
+  bool deep = 4 * STAGE <= 65536 && (long)tiles * splits <= 2 * 256 && per >= 4 && stages_pref() != 3;
+  if (deep || (stages_pref() == 4 && 4 * STAGE <= 65536))
+    hipLaunchKernelGGL((igemm_dma_kernel<T, CFG, LA, LB, 4>), grid, dim3(256), 0, st, la, lb, ep, rm,
+                       M, N, ktiles, per, xsplits);
+  else if (sizeof(T) == 2 && !ep.atomic && !ep.out_f32 && !ep.preact && ep.act == CLITE_ACT_NONE && !ep.dact_aux && ep.drop_p <= 0.f && !ep.residual && !ep.bn_y &&
+           !ep.mask_after_residual)
+    // plain bf16 store (+ bias, + column statistics): the branch-free epilogue instantiation
+    hipLaunchKernelGGL((igemm_dma_kernel<T, CFG, LA, LB, 3, 2>), grid, dim3(256), 0, st, la, lb, ep, rm,
+                       M, N, ktiles, per, xsplits);
+  else
+    hipLaunchKernelGGL((igemm_dma_kernel<T, CFG, LA, LB, 3>), grid, dim3(256), 0, st, la, lb, ep, rm,
+                       M, N, ktiles, per, xsplits);
   return (int)hipGetLastError();
 }
 
@@ -457,18 +431,18 @@ int gemm_nt(const void* A, int lda, const void* B, int ldb, int M, int N, int K,
   int splits = ep->atomic ? fewtile_splits(M, N, (K + BK - 1) / BK) : 1;
   if (int sk = splitk_plan<T>(*ep, M, N, (K + BK - 1) / BK)) {
     clite_epilogue e1 = splitk_partial(*ep, N);
-    GatherKC<T, 128, BK, false> la{A, ab, geom_dense(M, K, lda)};
-    GatherKC<T, 128, BK, false> lb{B, bb, geom_dense(N, K, ldb)};
+    DmaKC<T, 128, BK, false> la{A, ab, geom_dense(M, K, lda)};
+    DmaKC<T, 128, BK, false> lb{B, bb, geom_dense(N, K, ldb)};
     int rc = launch<T, typename Cfg<T>::C128>(la, lb, e1, M, N, K, sk, st);
     return rc ? rc : splitk_finish<T>(*ep, M, N, st);
   }
   if (N <= 64) {
-    GatherKC<T, 256, BK, false> la{A, ab, geom_dense(M, K, lda)};
-    GatherKC<T, 64, BK, false> lb{B, bb, geom_dense(N, K, ldb)};
+    DmaKC<T, 256, BK, false> la{A, ab, geom_dense(M, K, lda)};
+    DmaKC<T, 64, BK, false> lb{B, bb, geom_dense(N, K, ldb)};
     return launch<T, typename Cfg<T>::C256x64>(la, lb, *ep, M, N, K, splits, st);
   }
-  GatherKC<T, 128, BK, false> la{A, ab, geom_dense(M, K, lda)};
-  GatherKC<T, 128, BK, false> lb{B, bb, geom_dense(N, K, ldb)};
+  DmaKC<T, 128, BK, false> la{A, ab, geom_dense(M, K, lda)};
+  DmaKC<T, 128, BK, false> lb{B, bb, geom_dense(N, K, ldb)};
   return launch<T, typename Cfg<T>::C128>(la, lb, *ep, M, N, K, splits, st);
 }
 
@@ -479,18 +453,18 @@ int gemm_nn(const void* A, int lda, const void* B, int ldb, int M, int N, int K,
   int splits = ep->atomic ? fewtile_splits(M, N, (K + BK - 1) / BK) : 1;
   if (int sk = splitk_plan<T>(*ep, M, N, (K + BK - 1) / BK)) {
     clite_epilogue e1 = splitk_partial(*ep, N);
-    GatherKC<T, 128, BK, false> la{A, ab, geom_dense(M, K, lda)};
-    StridedXC<T, 128, BK> lb{B, bb, ldb, N, K, 1};
+    DmaKC<T, 128, BK, false> la{A, ab, geom_dense(M, K, lda)};
+    DmaXCStrided<T, 128, BK> lb{B, bb, ldb, N, K, 1};
     int rc = launch<T, typename Cfg<T>::C128>(la, lb, e1, M, N, K, sk, st);
     return rc ? rc : splitk_finish<T>(*ep, M, N, st);
   }
   if (N <= 64) {
-    GatherKC<T, 256, BK, false> la{A, ab, geom_dense(M, K, lda)};
-    StridedXC<T, 64, BK> lb{B, bb, ldb, N, K, 1};
+    DmaKC<T, 256, BK, false> la{A, ab, geom_dense(M, K, lda)};
+    DmaXCStrided<T, 64, BK> lb{B, bb, ldb, N, K, 1};
     return launch<T, typename Cfg<T>::C256x64>(la, lb, *ep, M, N, K, splits, st);
   }
-  GatherKC<T, 128, BK, false> la{A, ab, geom_dense(M, K, lda)};
-  StridedXC<T, 128, BK> lb{B, bb, ldb, N, K, 1};
+  DmaKC<T, 128, BK, false> la{A, ab, geom_dense(M, K, lda)};
+  DmaXCStrided<T, 128, BK> lb{B, bb, ldb, N, K, 1};
   return launch<T, typename Cfg<T>::C128>(la, lb, *ep, M, N, K, splits, st);
 }
 
@@ -499,8 +473,8 @@ int gemm_tn(const void* A, int lda, const void* B, int ldb, int M, int N, int K,
   constexpr int BK = Cfg<T>::BK;
   uint32_t ab = span_bytes(K, M, lda, sizeof(T)), bb = span_bytes(K, N, ldb, sizeof(T));
   int splits = ep->atomic ? pick_splits(M, N, (K + BK - 1) / BK) : 1;
-  StridedXC<T, 128, BK> la{A, ab, lda, M, K, 1};
-  StridedXC<T, 128, BK> lb{B, bb, ldb, N, K, 1};
+  DmaXCStrided<T, 128, BK> la{A, ab, lda, M, K, 1};
+  DmaXCStrided<T, 128, BK> lb{B, bb, ldb, N, K, 1};
   return launch<T, typename Cfg<T>::C128>(la, lb, *ep, M, N, K, splits, st);
 }
 
@@ -543,18 +517,18 @@ int conv_fwd(const void* x, const void* w, const clite_conv& c, const clite_epil
   if constexpr (sizeof(T) == 2) {
     // 3 x 3 / stride 1, 64 -> 64: the patch-resident kernel (conv_patch.hip) — automatic policy only; the deterministic mode keeps the path whose
     // statistics come from colstats_det
-    if (use_dma() && !deterministic() && tile_policy_value() == 0) {
+    if (!deterministic() && tile_policy_value() == 0) {
       const int rc = launch_conv3x3_patch(x, w, c, *ep, false, st);
       if (rc != WIDE_NOT_TAKEN) return rc;
     }
   }
   if (c.K <= 64) {
-    GatherKC<T, 256, BK, false> la{x, xb, geom_fwd(c)};
-    GatherKC<T, 64, BK, false> lb{w, wb, geom_dense(c.K, Ktot)};
+    DmaKC<T, 256, BK, false> la{x, xb, geom_fwd(c)};
+    DmaKC<T, 64, BK, false> lb{w, wb, geom_dense(c.K, Ktot)};
     return launch<T, typename Cfg<T>::C256x64>(la, lb, *ep, M, c.K, Ktot, 1, st);
   }
-  GatherKC<T, 128, BK, false> la{x, xb, geom_fwd(c)};
-  GatherKC<T, 128, BK, false> lb{w, wb, geom_dense(c.K, Ktot)};
+  DmaKC<T, 128, BK, false> la{x, xb, geom_fwd(c)};
+  DmaKC<T, 128, BK, false> lb{w, wb, geom_dense(c.K, Ktot)};
   return launch<T, typename Cfg<T>::C128>(la, lb, *ep, M, c.K, Ktot, 1, st);
 }
 
@@ -566,7 +540,7 @@ int conv_dgrad(const void* dy, const void* w, const clite_conv& c, const clite_e
   uint32_t yb = (uint32_t)((size_t)c.N * c.Ho * c.Wo * c.K * sizeof(T)), wb = (uint32_t)((size_t)c.K * c.R * c.S * c.C * sizeof(T));
   if constexpr (WT) {
     if constexpr (sizeof(T) == 2) {
-      if (use_dma() && !deterministic() && tile_policy_value() == 0) {          // 3 x 3 / stride 1, 64 <- 64: conv_patch.hip
+      if (!deterministic() && tile_policy_value() == 0) {          // 3 x 3 / stride 1, 64 <- 64: conv_patch.hip
         const int rc = launch_conv3x3_patch(dy, w, c, *ep, true, st);
         if (rc != WIDE_NOT_TAKEN) return rc;
       }
@@ -576,12 +550,12 @@ int conv_dgrad(const void* dy, const void* w, const clite_conv& c, const clite_e
       RowMap rm;
       rm.on = 1; rm.div_hw = fastdiv_make(c.Ho * c.Wo); rm.div_w = fastdiv_make(c.Wo); rm.H = c.H; rm.W = c.W; rm.stride = c.stride; rm.off_h = 0; rm.off_w = 0;
       if (c.C <= 64) {
-        GatherKC<T, 256, BK, false> la{dy, yb, geom_dense(P, c.K)};
-        GatherKC<T, 64, BK, false> lb{w, wb, geom_dense(c.C, c.K)};
+        DmaKC<T, 256, BK, false> la{dy, yb, geom_dense(P, c.K)};
+        DmaKC<T, 64, BK, false> lb{w, wb, geom_dense(c.C, c.K)};
         return launch<T, typename Cfg<T>::C256x64>(la, lb, *ep, P, c.C, c.K, 1, st, rm);
       }
-      GatherKC<T, 128, BK, false> la{dy, yb, geom_dense(P, c.K)};
-      GatherKC<T, 128, BK, false> lb{w, wb, geom_dense(c.C, c.K)};
+      DmaKC<T, 128, BK, false> la{dy, yb, geom_dense(P, c.K)};
+      DmaKC<T, 128, BK, false> lb{w, wb, geom_dense(c.C, c.K)};
       return launch<T, typename Cfg<T>::C128>(la, lb, *ep, P, c.C, c.K, 1, st, rm);
     }
     RowMap rm{};
@@ -593,12 +567,12 @@ int conv_dgrad(const void* dy, const void* w, const clite_conv& c, const clite_e
       rm.on = 2; rm.div_hw = fastdiv_make(c.H * c.W); rm.div_w = fastdiv_make(c.W); rm.H = c.H; rm.W = c.W; rm.stride = 2; rm.off_h = 0; rm.off_w = 0;
     }
     if (c.C <= 64) {
-      GatherKC<T, 256, BK, true> la{dy, yb, geom_dgrad(c)};
-      GatherKC<T, 64, BK, false> lb{w, wb, geom_dense(c.C, Ktot)};
+      DmaKC<T, 256, BK, true> la{dy, yb, geom_dgrad(c)};
+      DmaKC<T, 64, BK, false> lb{w, wb, geom_dense(c.C, Ktot)};
       return launch<T, typename Cfg<T>::C256x64>(la, lb, *ep, M, c.C, Ktot, 1, st, rm);
     }
-    GatherKC<T, 128, BK, true> la{dy, yb, geom_dgrad(c)};
-    GatherKC<T, 128, BK, false> lb{w, wb, geom_dense(c.C, Ktot)};
+    DmaKC<T, 128, BK, true> la{dy, yb, geom_dgrad(c)};
+    DmaKC<T, 128, BK, false> lb{w, wb, geom_dense(c.C, Ktot)};
     return launch<T, typename Cfg<T>::C128>(la, lb, *ep, M, c.C, Ktot, 1, st, rm);
   }
   if (ep->residual_subsample > 1) return -1;          // (the transposed-weight entry point only)
@@ -610,21 +584,21 @@ int conv_dgrad(const void* dy, const void* w, const clite_conv& c, const clite_e
     RowMap rm;
     rm.on = 1; rm.div_hw = fastdiv_make(c.Ho * c.Wo); rm.div_w = fastdiv_make(c.Wo); rm.H = c.H; rm.W = c.W; rm.stride = c.stride; rm.off_h = 0; rm.off_w = 0;
     if (c.C <= 64) {
-      GatherKC<T, 256, BK, false> la{dy, yb, geom_dense(P, c.K)};
-      StridedXC<T, 64, BK> lb{w, wb, c.C, c.C, c.K, 1};
+      DmaKC<T, 256, BK, false> la{dy, yb, geom_dense(P, c.K)};
+      DmaXCStrided<T, 64, BK> lb{w, wb, c.C, c.C, c.K, 1};
       return launch<T, typename Cfg<T>::C256x64>(la, lb, *ep, P, c.C, c.K, 1, st, rm);
     }
-    GatherKC<T, 128, BK, false> la{dy, yb, geom_dense(P, c.K)};
-    StridedXC<T, 128, BK> lb{w, wb, c.C, c.C, c.K, 1};
+    DmaKC<T, 128, BK, false> la{dy, yb, geom_dense(P, c.K)};
+    DmaXCStrided<T, 128, BK> lb{w, wb, c.C, c.C, c.K, 1};
     return launch<T, typename Cfg<T>::C128>(la, lb, *ep, P, c.C, c.K, 1, st, rm);
   }
   if (c.C <= 64) {
-    GatherKC<T, 256, BK, true> la{dy, yb, geom_dgrad(c)};
-    StridedXC<T, 64, BK> lb{w, wb, c.R * c.S * c.C, c.C, c.K, c.R * c.S};
+    DmaKC<T, 256, BK, true> la{dy, yb, geom_dgrad(c)};
+    DmaXCStrided<T, 64, BK> lb{w, wb, c.R * c.S * c.C, c.C, c.K, c.R * c.S};
     return launch<T, typename Cfg<T>::C256x64>(la, lb, *ep, M, c.C, Ktot, 1, st);
   }
-  GatherKC<T, 128, BK, true> la{dy, yb, geom_dgrad(c)};
-  StridedXC<T, 128, BK> lb{w, wb, c.R * c.S * c.C, c.C, c.K, c.R * c.S};
+  DmaKC<T, 128, BK, true> la{dy, yb, geom_dgrad(c)};
+  DmaXCStrided<T, 128, BK> lb{w, wb, c.R * c.S * c.C, c.C, c.K, c.R * c.S};
   return launch<T, typename Cfg<T>::C128>(la, lb, *ep, M, c.C, Ktot, 1, st);
 }
 
@@ -653,21 +627,21 @@ int conv_dgrad_s2class(const void* dy, const void* wsub, const clite_conv& c, in
   uint32_t yb = (uint32_t)((size_t)c.N * c.Ho * c.Wo * c.K * sizeof(T)), wb = (uint32_t)((size_t)c.K * na * nb * c.C * sizeof(T));
   if constexpr (WT) {            // wsub = [C][na][nb][K]
     if (c.C <= 64) {
-      GatherKC<T, 256, BK, true> la{dy, yb, g};
-      GatherKC<T, 64, BK, false> lb{wsub, wb, geom_dense(c.C, Ktot)};
+      DmaKC<T, 256, BK, true> la{dy, yb, g};
+      DmaKC<T, 64, BK, false> lb{wsub, wb, geom_dense(c.C, Ktot)};
       return launch<T, typename Cfg<T>::C256x64>(la, lb, *ep, M, c.C, Ktot, 1, st, rm);
     }
-    GatherKC<T, 128, BK, true> la{dy, yb, g};
-    GatherKC<T, 128, BK, false> lb{wsub, wb, geom_dense(c.C, Ktot)};
+    DmaKC<T, 128, BK, true> la{dy, yb, g};
+    DmaKC<T, 128, BK, false> lb{wsub, wb, geom_dense(c.C, Ktot)};
     return launch<T, typename Cfg<T>::C128>(la, lb, *ep, M, c.C, Ktot, 1, st, rm);
   }
   if (c.C <= 64) {
-    GatherKC<T, 256, BK, true> la{dy, yb, g};
-    StridedXC<T, 64, BK> lb{wsub, wb, na * nb * c.C, c.C, c.K, na * nb};
+    DmaKC<T, 256, BK, true> la{dy, yb, g};
+    DmaXCStrided<T, 64, BK> lb{wsub, wb, na * nb * c.C, c.C, c.K, na * nb};
     return launch<T, typename Cfg<T>::C256x64>(la, lb, *ep, M, c.C, Ktot, 1, st, rm);
   }
-  GatherKC<T, 128, BK, true> la{dy, yb, g};
-  StridedXC<T, 128, BK> lb{wsub, wb, na * nb * c.C, c.C, c.K, na * nb};
+  DmaKC<T, 128, BK, true> la{dy, yb, g};
+  DmaXCStrided<T, 128, BK> lb{wsub, wb, na * nb * c.C, c.C, c.K, na * nb};
   return launch<T, typename Cfg<T>::C128>(la, lb, *ep, M, c.C, Ktot, 1, st, rm);
 }
 
@@ -679,17 +653,17 @@ int conv_wgrad(const void* dy, const void* x, const clite_conv& c, float* dw, hi
   clite_epilogue ep = {};
   ep.out = dw; ep.ldc = Ncols; ep.out_f32 = 1; ep.atomic = 1; ep.alpha = 1.f;
   if (c.K <= 64) {          // a 128-row tile would be half empty
-    StridedXC<T, 64, BK> la{dy, yb, c.K, c.K, P, 1};
-    GatherXC<T, 128, BK> lb{x, xb, geom_fwd(c)};
+    DmaXCStrided<T, 64, BK> la{dy, yb, c.K, c.K, P, 1};
+    DmaXCGather<T, 128, BK> lb{x, xb, geom_fwd(c)};
     return launch<T, typename Cfg<T>::C64x128>(la, lb, ep, c.K, Ncols, P, pick_splits(c.K, Ncols, (P + BK - 1) / BK, 64, 128, c.R * c.S > 1), st);
   }
   if (Ncols <= 64) {
-    StridedXC<T, 128, BK> la{dy, yb, c.K, c.K, P, 1};
-    GatherXC<T, 64, BK> lb{x, xb, geom_fwd(c)};
+    DmaXCStrided<T, 128, BK> la{dy, yb, c.K, c.K, P, 1};
+    DmaXCGather<T, 64, BK> lb{x, xb, geom_fwd(c)};
     return launch<T, typename Cfg<T>::C128x64>(la, lb, ep, c.K, Ncols, P, pick_splits(c.K, Ncols, (P + BK - 1) / BK, 128, 64, c.R * c.S > 1), st);
   }
-  StridedXC<T, 128, BK> la{dy, yb, c.K, c.K, P, 1};
-  GatherXC<T, 128, BK> lb{x, xb, geom_fwd(c)};
+  DmaXCStrided<T, 128, BK> la{dy, yb, c.K, c.K, P, 1};
+  DmaXCGather<T, 128, BK> lb{x, xb, geom_fwd(c)};
   int splits = pick_splits(c.K, Ncols, (P + BK - 1) / BK, 128, 128, c.R * c.S > 1);
   return launch<T, typename Cfg<T>::C128>(la, lb, ep, c.K, Ncols, P, splits, st);
 }
@@ -715,8 +689,8 @@ int check_stem(int dtype, int N, int Hp, int Wp, int Ho, int Wo) {
 template <typename T>
 int stem_fwd(const void* xpad, const void* wv, int N, int Hp, int Wp, int Ho, int Wo, const clite_epilogue* ep, hipStream_t st) {
   constexpr int BK = Cfg<T>::BK;
-  GatherKC<T, 256, BK, false> la{xpad, (uint32_t)((size_t)N * Hp * Wp * 4 * sizeof(T)), geom_stem(N, Hp, Wp, Ho, Wo)};
-  GatherKC<T, 64, BK, false> lb{wv, (uint32_t)(64 * 224 * sizeof(T)), geom_dense(64, 224)};
+  DmaKC<T, 256, BK, false> la{xpad, (uint32_t)((size_t)N * Hp * Wp * 4 * sizeof(T)), geom_stem(N, Hp, Wp, Ho, Wo)};
+  DmaKC<T, 64, BK, false> lb{wv, (uint32_t)(64 * 224 * sizeof(T)), geom_dense(64, 224)};
   return launch<T, typename Cfg<T>::C256x64>(la, lb, *ep, N * Ho * Wo, 64, 224, 1, st);
 }
 template <typename T>
@@ -726,8 +700,8 @@ int stem_wgrad(const void* dy, const void* xpad, int N, int Hp, int Wp, int Ho, 
   clite_epilogue ep = {};
   ep.out = dwv; ep.ldc = 224; ep.out_f32 = 1; ep.atomic = 1; ep.alpha = 1.f;
   // 64 output channels: the 64-row tile of conv_wgrad (a 128-row tile is half empty: twice the MFMAs and dy fragment reads; 198.7 -> 181.2 us)
-  StridedXC<T, 64, BK> la{dy, (uint32_t)((size_t)P * 64 * sizeof(T)), 64, 64, P, 1};
-  GatherXC<T, 128, BK> lb{xpad, (uint32_t)((size_t)N * Hp * Wp * 4 * sizeof(T)), geom_stem(N, Hp, Wp, Ho, Wo)};
+  DmaXCStrided<T, 64, BK> la{dy, (uint32_t)((size_t)P * 64 * sizeof(T)), 64, 64, P, 1};
+  DmaXCGather<T, 128, BK> lb{xpad, (uint32_t)((size_t)N * Hp * Wp * 4 * sizeof(T)), geom_stem(N, Hp, Wp, Ho, Wo)};
   int splits = pick_splits(64, 224, (P + BK - 1) / BK, 64, 128, true);
   return launch<T, typename Cfg<T>::C64x128>(la, lb, ep, 64, 224, P, splits, st);
 }
@@ -818,17 +792,16 @@ extern "C" int clite_conv_dgrad_bnfold(const void* pair, const void* w2, int M, 
   g.div_w = fastdiv_make(M);
   const uint32_t ab = (uint32_t)((size_t)2 * M * K * sizeof(T)), wb = (uint32_t)((size_t)Cin * 2 * K * sizeof(T));
   hipStream_t st = (hipStream_t)stream;
-  if (use_dma()) {          // K = 256, Cin = 64 (the 56 x 56 stage): the streaming kernel of fold_dgrad.hip
-    const int rc = launch_fold_dgrad_rows(pair, w2, M, K, Cin, *ep, st);
-    if (rc != WIDE_NOT_TAKEN) return rc;
-  }
+  // K = 256, Cin = 64 (the 56 x 56 stage): the streaming kernel of fold_dgrad.hip
+  const int rc = launch_fold_dgrad_rows(pair, w2, M, K, Cin, *ep, st);
+  if (rc != WIDE_NOT_TAKEN) return rc;
   if (Cin <= 64) {
-    GatherKC<T, 256, BK, true> la{pair, ab, g};
-    GatherKC<T, 64, BK, false> lb{w2, wb, geom_dense(Cin, 2 * K)};
+    DmaKC<T, 256, BK, true> la{pair, ab, g};
+    DmaKC<T, 64, BK, false> lb{w2, wb, geom_dense(Cin, 2 * K)};
     return launch<T, typename Cfg<T>::C256x64>(la, lb, *ep, M, Cin, 2 * K, 1, st);
   }
-  GatherKC<T, 128, BK, true> la{pair, ab, g};
-  GatherKC<T, 128, BK, false> lb{w2, wb, geom_dense(Cin, 2 * K)};
+  DmaKC<T, 128, BK, true> la{pair, ab, g};
+  DmaKC<T, 128, BK, false> lb{w2, wb, geom_dense(Cin, 2 * K)};
   return launch<T, typename Cfg<T>::C128>(la, lb, *ep, M, Cin, 2 * K, 1, st);
 }
 extern "C" int clite_conv_dgrad_s2class_wt(const void* dy, const void* wtsub, const clite_conv* cv, int ph, int pw, const clite_epilogue* ep, void* stream) {

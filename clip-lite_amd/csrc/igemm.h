@@ -9,13 +9,9 @@
 //     LDS images are [k][x] and the MFMA fragments come from ds_read_b64_tr_b16 transposed reads
 //   * every nn.Linear of BERT (encoder.py:165-196) and of the MI heads / priors (loss.py:12-53).
 //
-// Operand images in LDS:
-//   KC (k-contiguous in memory): [ROWS][BK] bf16, row pitch BK*2+16 B  -> conflict-free ds_read_b128 fragments
-//   XC (x-contiguous in memory, contraction index is the slow one): [BK][ROWS] bf16, pitch ROWS*2+64 B
-//       -> conflict-free ds_read_b64_tr_b16 (a 32-lane half covers 4 k-rows x 64 B on disjoint banks)
-// Staging is global -> VGPR (buffer loads: out-of-range = 0, which implements im2col padding, ragged
-// tile edges and K tails without branches) -> ds_write_b128, double-buffered, one barrier per K tile;
-// the loads of tile t+1 are issued before the MFMAs of tile t and written after them.
+// This header holds what every kernel of the family shares: the conv geometry (FastDiv, ConvGeom, RowMap), the tile configuration (TileCfg) and
+// the epilogues (generic fused, plain bf16 store, BatchNorm backward) with their tuning constants. The operand loaders (global -> LDS by DMA,
+// swizzled LDS images) and the main loops are in igemm_dma.h; the 8-wave wide-K kernels in igemm_wide.h.
 #ifndef CLITE_IGEMM_H
 #define CLITE_IGEMM_H
 #include "intrin.h"
@@ -39,9 +35,6 @@
 #ifndef CLITE_BN_EARLY
 #define CLITE_BN_EARLY 4           // rows of epilogue operands igemm_dma_bn_kernel requests BEFORE a tile's main loop (specialised forms; 0: none)
 #endif
-#ifndef CLITE_BN_HALF
-#define CLITE_BN_HALF 0            // 1: half-tile staging + three workgroups per CU (measured: no gain)
-#endif
 
 namespace clite {
 
@@ -63,217 +56,6 @@ struct ConvGeom {
   int concat;         // 1: the "window" is a K-concatenation of R tensors laid out back to back (clite_conv_dgrad_bnfold: H = R slots, W = rows) —
                       // a short-K 1 x 1 problem for the launch policies, not a sliding window
   FastDiv div_hw, div_w;  // by RH*RW and by RW
-};
-
-// ------------------------------------------------------------------------------------------------
-// KC gather loader: rows = pixels of the row space, k = (r, s, c) with c contiguous.
-// DGRAD=false: hi = rh*stride - pad + r.   DGRAD=true: hi = (rh + pad - r) / stride when divisible.
-template <typename T, int ROWS, int BK, bool DGRAD>
-struct GatherKC {
-  static constexpr int EPC = 16 / (int)sizeof(T);    // elements per 16-B chunk
-  static constexpr int CPR = BK / EPC;               // 16-B chunks per row
-  static constexpr int NCH = ROWS * CPR / 256;       // chunks per thread
-  static constexpr int PITCH = BK * (int)sizeof(T) + 16;
-  static constexpr int BYTES = ROWS * PITCH;
-  static constexpr bool XC = false;
-  const void* ptr;
-  uint32_t bytes;
-  ConvGeom g;
-
-  struct State {
-    rsrc_t rs;
-    int base[NCH], h0[NCH], w0[NCH];  // base = n*sN, or -1 when the row is out of range
-    int kc8;                          // element offset of this thread's chunk inside the K tile
-    int r, s, c0;
-  };
-  DEV void init(State& st, int row0, int tid, int t_begin) const {
-    st.rs = make_rsrc(ptr, bytes);
-    st.kc8 = (tid % CPR) * EPC;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      int row = row0 + (tid + 256 * i) / CPR;
-      if (row < g.rows) {
-        uint32_t n = fd_div(row, g.div_hw);
-        uint32_t rem = row - n * g.div_hw.d;
-        uint32_t rh = fd_div(rem, g.div_w);
-        uint32_t rw = rem - rh * g.div_w.d;
-        st.base[i] = n * g.sN;
-        if (DGRAD) { st.h0[i] = rh + g.pad; st.w0[i] = rw + g.padw; }
-        else { st.h0[i] = rh * g.stride - g.pad; st.w0[i] = rw * g.stride - g.padw; }
-      } else {
-        st.base[i] = -1; st.h0[i] = 0; st.w0[i] = 0;
-      }
-    }
-    int k0 = t_begin * BK;
-    int rs = k0 / g.C;
-    st.c0 = k0 - rs * g.C;
-    st.r = rs / g.S;
-    st.s = rs - st.r * g.S;
-  }
-  DEV void load(State& st, u32x4 (&regs)[NCH]) const {
-    int c = st.c0 + st.kc8;
-    bool kvalid = c < g.C && st.r < g.R;
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      int hi, wi;
-      bool v = kvalid && st.base[i] >= 0;
-      if (DGRAD) {
-        int hh = st.h0[i] - st.r, ww = st.w0[i] - st.s;
-        if (g.stride == 1) { hi = hh; wi = ww; }
-        else if (g.stride == 2) { v = v && ((hh | ww) & 1) == 0; hi = hh >> 1; wi = ww >> 1; }
-        else { v = v && hh % g.stride == 0 && ww % g.stride == 0; hi = hh / g.stride; wi = ww / g.stride; }
-        v = v && hh >= 0 && ww >= 0;
-      } else {
-        hi = st.h0[i] + st.r; wi = st.w0[i] + st.s;
-      }
-      v = v && (unsigned)hi < (unsigned)g.H && (unsigned)wi < (unsigned)g.W;
-      uint32_t off = v ? (uint32_t)(st.base[i] + hi * g.sH + wi * g.sW + c) * (uint32_t)sizeof(T) : OOB_OFF;
-      regs[i] = buf_load16(st.rs, off);
-    }
-    st.c0 += BK;
-    if (st.c0 >= g.C) { st.c0 = 0; if (++st.s == g.S) { st.s = 0; ++st.r; } }
-  }
-  DEV static void store(char* lds, int tid, const u32x4 (&regs)[NCH]) {
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      int c = tid + 256 * i;
-      *(u32x4*)(lds + (c / CPR) * PITCH + (c % CPR) * 16) = regs[i];
-    }
-  }
-  // bf16: MFMA 32x32x16 fragment for the 32-row block starting at x0, k-step ks (16 deep)
-  DEV static bf16x8 frag(const char* lds, int x0, int ks, int lane) {
-    Chunk16 ch;
-    ch.u = *(const u32x4*)(lds + (x0 + (lane & 31)) * PITCH + (ks * 16 + 8 * (lane >> 5)) * 2);
-    return ch.h;
-  }
-  // f32: MFMA 32x32x2 operand (one value per lane), k-step kk (2 deep)
-  DEV static float frag32(const char* lds, int x0, int kk, int lane) {
-    return *(const float*)(lds + (x0 + (lane & 31)) * PITCH + (kk * 2 + (lane >> 5)) * 4);
-  }
-};
-
-// ------------------------------------------------------------------------------------------------
-// XC strided loader: element (k, x) at ptr[(k0+krow)*ld + rs*Cx + x]; k = (rs, kk) with kk < Ck.
-// Serves: weights for dgrad (W[co][r][s][ci]: ld = R*S*Cin, Cx = Cin, Ck = Cout, RS = R*S),
-//         linear dgrad (W[n][k]: ld = K, Cx = K, Ck = N, RS = 1), wgrad's dY ([P][Cout]: ld = Cx = Cout, Ck = P).
-template <typename T, int COLS, int BK>
-struct StridedXC {
-  static constexpr int EPC = 16 / (int)sizeof(T);
-  static constexpr int CPR = COLS / EPC;
-  static constexpr int NCH = BK * CPR / 256;
-  static constexpr int RPS = 256 / CPR;              // k-rows per sweep of the block
-  static constexpr int PITCH = COLS * (int)sizeof(T) + 64;
-  static constexpr int BYTES = BK * PITCH;
-  static constexpr bool XC = true;
-  const void* ptr;
-  uint32_t bytes;
-  int ld, Cx, Ck, RS;
-
-  struct State {
-    rsrc_t rs_;
-    int x, krow0;
-    bool xvalid;
-    int rs, k0;
-  };
-  DEV void init(State& st, int x0, int tid, int t_begin) const {
-    st.rs_ = make_rsrc(ptr, bytes);
-    st.x = x0 + (tid % CPR) * EPC;
-    st.xvalid = st.x < Cx;
-    st.krow0 = tid / CPR;
-    int kk = t_begin * BK;
-    st.rs = (RS == 1) ? 0 : kk / Ck;
-    st.k0 = kk - st.rs * Ck;
-  }
-  DEV void load(State& st, u32x4 (&regs)[NCH]) const {
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      int k = st.k0 + st.krow0 + i * RPS;
-      bool v = st.xvalid && k < Ck && st.rs < RS;
-      uint32_t off = v ? (uint32_t)(k * ld + st.rs * Cx + st.x) * (uint32_t)sizeof(T) : OOB_OFF;
-      regs[i] = buf_load16(st.rs_, off);
-    }
-    st.k0 += BK;
-    if (st.k0 >= Ck && RS > 1) { st.k0 = 0; ++st.rs; }
-  }
-  DEV static void store(char* lds, int tid, const u32x4 (&regs)[NCH]) {
-#pragma unroll
-    for (int i = 0; i < NCH; ++i)
-      *(u32x4*)(lds + (tid / CPR + i * RPS) * PITCH + (tid % CPR) * 16) = regs[i];
-  }
-  DEV static bf16x8 frag(const char* lds, int x0, int ks, int lane) {
-    // lane 4q+p of each 16-lane group addresses k-row q, columns 4p..4p+3 of a [4 k][16 x] block
-    int x = x0 + 16 * ((lane >> 4) & 1) + 4 * (lane & 3);
-    int k = ks * 16 + 8 * (lane >> 5) + ((lane >> 2) & 3);
-    const char* p = lds + k * PITCH + x * 2;
-    s16x4 lo = lds_read_tr16(p);
-    s16x4 hi = lds_read_tr16(p + 4 * PITCH);
-    union { s16x4 v[2]; bf16x8 h; } u;
-    u.v[0] = lo; u.v[1] = hi;
-    return u.h;
-  }
-  DEV static float frag32(const char* lds, int x0, int kk, int lane) {
-    return *(const float*)(lds + (kk * 2 + (lane >> 5)) * PITCH + (x0 + (lane & 31)) * 4);
-  }
-};
-
-// ------------------------------------------------------------------------------------------------
-// XC gather loader (wgrad's activation operand): k = output pixel p -> (n, ho, wo); x = (r, s, ci).
-template <typename T, int COLS, int BK>
-struct GatherXC {
-  static constexpr int EPC = 16 / (int)sizeof(T);
-  static constexpr int CPR = COLS / EPC;
-  static constexpr int NCH = BK * CPR / 256;
-  static constexpr int RPS = 256 / CPR;
-  static constexpr int PITCH = COLS * (int)sizeof(T) + 64;
-  static constexpr int BYTES = BK * PITCH;
-  static constexpr bool XC = true;
-  const void* ptr;
-  uint32_t bytes;
-  ConvGeom g;   // rows = N*Ho*Wo pixels (the contraction index); RH,RW = Ho,Wo
-
-  struct State {
-    rsrc_t rs_;
-    int xoff;      // r*sH + s*sW + ci, or -1 if this column is out of range
-    int r, s;
-    int krow0, p0;
-  };
-  DEV void init(State& st, int x0, int tid, int t_begin) const {
-    st.rs_ = make_rsrc(ptr, bytes);
-    int x = x0 + (tid % CPR) * EPC;
-    int rs = x / g.C;
-    int ci = x - rs * g.C;
-    st.r = rs / g.S;
-    st.s = rs - st.r * g.S;
-    st.xoff = (x < g.R * g.S * g.C) ? ci : -1;
-    st.krow0 = tid / CPR;
-    st.p0 = t_begin * BK;
-  }
-  DEV void load(State& st, u32x4 (&regs)[NCH]) const {
-#pragma unroll
-    for (int i = 0; i < NCH; ++i) {
-      int p = st.p0 + st.krow0 + i * RPS;
-      bool v = st.xoff >= 0 && p < g.rows;
-      uint32_t n = fd_div(p, g.div_hw);
-      uint32_t rem = p - n * g.div_hw.d;
-      uint32_t ho = fd_div(rem, g.div_w);
-      uint32_t wo = rem - ho * g.div_w.d;
-      int hi = (int)ho * g.stride - g.pad + st.r;
-      int wi = (int)wo * g.stride - g.padw + st.s;
-      v = v && (unsigned)hi < (unsigned)g.H && (unsigned)wi < (unsigned)g.W;
-      uint32_t off = v ? (uint32_t)((int)n * g.sN + hi * g.sH + wi * g.sW + st.xoff) * (uint32_t)sizeof(T) : OOB_OFF;
-      regs[i] = buf_load16(st.rs_, off);
-    }
-    st.p0 += BK;
-  }
-  DEV static void store(char* lds, int tid, const u32x4 (&regs)[NCH]) {
-    StridedXC<T, COLS, BK>::store(lds, tid, regs);
-  }
-  DEV static bf16x8 frag(const char* lds, int x0, int ks, int lane) {
-    return StridedXC<T, COLS, BK>::frag(lds, x0, ks, lane);
-  }
-  DEV static float frag32(const char* lds, int x0, int kk, int lane) {
-    return StridedXC<T, COLS, BK>::frag32(lds, x0, kk, lane);
-  }
 };
 
 // ------------------------------------------------------------------------------------------------
@@ -362,7 +144,7 @@ struct TileCfg {
   static constexpr int EPI_BYTES = WM * EPI_PITCH;
 };
 
-// Fused epilogue shared by the register-staged and the LDS-DMA kernels. `smem` must be free (all waves past their last
+// Fused epilogue of the LDS-DMA kernels. `smem` must be free (all waves past their last
 // fragment read) and at least max(CFG::EPI_BYTES, 16 KB) large.
 // HEAVY = the BatchNorm-backward form (clite_epilogue.bn_y / mask_after_residual, operands prefetched two rows at a time). It costs
 // ~45 more registers than the plain form, which would take every kernel from 3 to 2 workgroups per CU, so it is a separate
@@ -759,6 +541,21 @@ struct BnRows {
   }
 };
 
+// the workgroup's accumulator tile as an f32 [BM][EPI_PITCH] image in LDS (MFMA 32 x 32 layout: register r of lane l is row (r & 3) + 8 (r >> 2) + 4 (l >> 5), column l & 31)
+template <class CFG>
+DEV void stage_acc(const f32x16 (&acc)[CFG::RM][CFG::RN], char* smem, int wm0, int wn0, int lane) {
+#pragma unroll
+  for (int i = 0; i < CFG::RM; ++i)
+#pragma unroll
+    for (int j = 0; j < CFG::RN; ++j)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        int row = wm0 + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        int col = wn0 + j * 32 + (lane & 31);
+        *(float*)(smem + row * CFG::EPI_PITCH + col * 4) = acc[i][j][r];
+      }
+}
+
 // (FORM 3, round 4 = FORM 2 with the residual read through RowMap's subsampled-row map: the block-input gradient of a stride-2 downsample block.)
 // FORM: what the launch needs, fixed at compile time. 0 = every combination clite_epilogue allows in this form, decided by run-time flags and
 // selects (tests, f32, the tensor form of the mask). 1 / 2 = the two forms the bf16 ResNet backward launches — packed relu' bits, BatchNorm input,
@@ -775,38 +572,8 @@ DEV void igemm_epilogue_bn(f32x16 (&acc)[CFG::RM][CFG::RN], BnEpiState& st, BnRo
   const int ecol = (tid % CPRE) * 8, erow0 = tid / CPRE;
   const int gcol = n0 + ecol;
   const bool colok = gcol < N;
-  // The accumulator tile goes through LDS in NP passes of BM / NP rows (NP = 1: the whole tile at once, 68 KB = two workgroups per CU; NP = 2 in
-  // the specialised forms: 34 KB, under the 48 KB operand ring, so THREE workgroups fit a CU). The ablations of round 3 showed the launch's
-  // parts — compute, operand DMA, epilogue loads, epilogue stores — adding up instead of overlapping: with two waves per SIMD both are
-  // usually parked on memory at the same time; a third resident workgroup is what hides that.
-  // Pass p takes the p-th 32-row MFMA block of EVERY wave (not the first half of the waves), so that each wave's accumulators die by halves
-  // and no wave carries all 64 of them through the VALU-heavy row loop of the other pass: tile row R belongs to pass (R / 32) % RM and sits at
-  // image row (R / 32 / RM) * 32 + R % 32.
-  constexpr int NP = (FORM && CLITE_BN_HALF) ? RM : 1, QPP = ROWS_PT / NP;
-  static_assert(NP == 1 || (RM == 2 && ROWS_PT % NP == 0 && 32 % RPSE == 0), "pass structure");
-  auto stage = [&](int p) {
-#pragma unroll
-    for (int i = 0; i < RM; ++i) {
-      if (NP > 1 && i != p) continue;
-#pragma unroll
-      for (int j = 0; j < RN; ++j)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          int row = (NP > 1 ? (wm0 / CFG::WM) * 32 : wm0 + i * 32) + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-          int col = wn0 + j * 32 + (lane & 31);
-          *(float*)(smem + row * CFG::EPI_PITCH + col * 4) = acc[i][j][r];
-        }
-    }
-  };
-  // processing order of the thread's ROWS_PT rows: pass 0's rows first. Row index q (tile row erow0 + q * RPSE) -> pass ((q * RPSE) / 32) % NP
-  auto row_of = [](int k) {          // k-th row in processing order
-    if (NP == 1) return k;
-    int p = k / QPP, n = k % QPP, seen = 0;
-    for (int q = 0; q < ROWS_PT; ++q)
-      if (((q * RPSE) / 32) % NP == p) { if (seen == n) return q; ++seen; }
-    return 0;
-  };
-  stage(0);
+  // The accumulator tile goes through LDS whole: 68 KB, two workgroups per CU (staging it by halves for a third one gained nothing: below)
+  stage_acc<CFG>(acc, smem, wm0, wn0, lane);
   float (&bn_mean)[8] = st.bn_mean;
   float (&csum)[8] = st.csum;
   float (&csq)[8] = st.csq;
@@ -816,8 +583,7 @@ DEV void igemm_epilogue_bn(f32x16 (&acc)[CFG::RM][CFG::RN], BnEpiState& st, BnRo
   //  * staging one wave row at a time (34 KB, under the operand ring) + __launch_bounds__(256, 3) for three workgroups per CU: the
   //    allocator then spills 20 registers and the launches get slower — 256 -> 64 191 -> 267 us, 64 -> 256 97 -> 116, step 18.7 -> 19.2 ms.
 
-  constexpr int AHEAD = (FORM && CLITE_BN_HALF) ? 2 : (FORM ? CLITE_BN_AHEAD_FORM : CLITE_BN_AHEAD);
-  static_assert(NREQ == 0 || NP == 1, "early requests assume the whole-tile staging order");
+  constexpr int AHEAD = FORM ? CLITE_BN_AHEAD_FORM : CLITE_BN_AHEAD;
   const bool has_bits = FORM ? FORM != 4 : ep.relu_bits != nullptr, has_aux = FORM ? false : ep.dact_aux != nullptr, has_y = FORM ? FORM != 4 : ep.bn_y != nullptr;
   const bool mask_after = FORM ? (FORM == 2 || FORM == 3) : ep.mask_after_residual != 0;
   const bool to_f32 = FORM ? false : (ep.out_f32 || sizeof(T) == 4);
@@ -827,21 +593,14 @@ DEV void igemm_epilogue_bn(f32x16 (&acc)[CFG::RM][CFG::RN], BnEpiState& st, BnRo
   bool (&okr)[ROWS_PT] = rows.okr;
   auto request = [&](int q) { rows.request(q, ep, rm, M, N, m0, n0, tid); };
 #pragma unroll
-  for (int k = NREQ; k < AHEAD && k < ROWS_PT; ++k) request(row_of(k));
+  for (int k = NREQ; k < AHEAD && k < ROWS_PT; ++k) request(k);
   lds_barrier();
   EPI_STAMP(6);
   BN_EPI_PHASE(4);        // accumulators staged, first requests issued
 #pragma unroll
-  for (int k = 0; k < ROWS_PT; ++k) {
-    const int q = row_of(k);
-    if (NP > 1 && k > 0 && k % QPP == 0) {          // next pass: every thread is past its reads of the previous image, then every wave stages
-      lds_barrier();
-      stage(k / QPP);
-      lds_barrier();
-    }
-    if (k + AHEAD < ROWS_PT && k + AHEAD >= NREQ) request(row_of(k + AHEAD));
-    const int irow = NP == 1 ? erow0 + q * RPSE : ((erow0 + q * RPSE) / 32 / RM) * 32 + (erow0 + q * RPSE) % 32;
-    const float* src = (const float*)(smem + irow * CFG::EPI_PITCH + ecol * 4);
+  for (int q = 0; q < ROWS_PT; ++q) {
+    if (q + AHEAD < ROWS_PT && q + AHEAD >= NREQ) request(q + AHEAD);
+    const float* src = (const float*)(smem + (erow0 + q * RPSE) * CFG::EPI_PITCH + ecol * 4);
     f32x4 v0 = *(const f32x4*)src, v1 = *(const f32x4*)(src + 4);
     float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
     float msk[8], av[8], rv[8], yv[8];
@@ -898,106 +657,6 @@ DEV void igemm_epilogue_bn(f32x16 (&acc)[CFG::RM][CFG::RN], BnEpiState& st, BnRo
   EPI_STAMP(7);
   BN_EPI_PHASE(5);        // row loop: operands in, results out, statistics
 }
-
-#if defined(CLITE_DIAG) && CLITE_DIAG
-// Round-1 register-staged engine (global -> VGPR -> ds_write_b128, two LDS stages): diagnostic builds only, as the A/B yardstick for the
-// LDS-DMA kernels of igemm_dma.h. The product library does not contain it.
-template <typename T, class CFG, class LA, class LB>
-__global__ __launch_bounds__(256) void igemm_kernel(LA la, LB lb, Epilogue ep, RowMap rm, int M, int N, int ktiles, int ktiles_per_split) {
-  constexpr int BM = CFG::BM, BN = CFG::BN, BK = CFG::BK;
-  constexpr int RM = CFG::RM, RN = CFG::RN;
-  constexpr int STAGE = LA::BYTES + LB::BYTES;
-  constexpr int SMEM = (2 * STAGE > CFG::EPI_BYTES) ? 2 * STAGE : CFG::EPI_BYTES;
-  __shared__ __attribute__((aligned(16))) char smem[SMEM];
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = tid >> 6;
-  const int wm0 = (wave / CFG::WAVES_N) * CFG::WM;
-  const int wn0 = (wave % CFG::WAVES_N) * CFG::WN;
-
-  // XCD-aware tile order: workgroups b and b+8 share an XCD (and its 4 MiB L2) under round-robin dispatch, so give
-  // each XCD a contiguous run of logical tiles (bijective for any grid size); placement affects speed only.
-  const int nwg = gridDim.x, xcd = blockIdx.x & 7, xq = nwg >> 3, xr = nwg & 7;
-  const int wg = (xcd < xr ? xcd * (xq + 1) : xr * (xq + 1) + (xcd - xr) * xq) + (blockIdx.x >> 3);
-  const int tiles_n = (N + BN - 1) / BN;
-  const int tm = wg / tiles_n;
-  const int tn = wg - tm * tiles_n;
-  const int m0 = tm * BM, n0 = tn * BN;
-  const int t_begin = blockIdx.z * ktiles_per_split;
-  int t_end = t_begin + ktiles_per_split;
-  if (t_end > ktiles) t_end = ktiles;
-
-  typename LA::State sa;
-  typename LB::State sb;
-  la.init(sa, m0, tid, t_begin);
-  lb.init(sb, n0, tid, t_begin);
-
-  f32x16 acc[RM][RN];
-#pragma unroll
-  for (int i = 0; i < RM; ++i)
-#pragma unroll
-    for (int j = 0; j < RN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  u32x4 ra[LA::NCH], rb[LB::NCH];
-  if (t_begin < t_end) {
-    la.load(sa, ra);
-    lb.load(sb, rb);
-    LA::store(smem, tid, ra);
-    LB::store(smem + LA::BYTES, tid, rb);
-  }
-  __syncthreads();
-
-  for (int t = t_begin; t < t_end; ++t) {
-    const int cur = (t - t_begin) & 1;
-    const bool more = t + 1 < t_end;
-    if (more) {
-      la.load(sa, ra);
-      lb.load(sb, rb);
-    }
-    const char* abuf = smem + cur * STAGE;
-    const char* bbuf = abuf + LA::BYTES;
-    if constexpr (sizeof(T) == 2) {
-#pragma unroll
-      for (int ks = 0; ks < BK / 16; ++ks) {
-        bf16x8 af[RM], bfr[RN];
-#pragma unroll
-        for (int i = 0; i < RM; ++i) af[i] = LA::frag(abuf, wm0 + i * 32, ks, lane);
-#pragma unroll
-        for (int j = 0; j < RN; ++j) bfr[j] = LB::frag(bbuf, wn0 + j * 32, ks, lane);
-#pragma unroll
-        for (int i = 0; i < RM; ++i)
-#pragma unroll
-          for (int j = 0; j < RN; ++j) acc[i][j] = mfma32_bf16(af[i], bfr[j], acc[i][j]);
-      }
-    } else {   // exact-f32 parity mode: v_mfma_f32_32x32x2_f32, a k-ordered fmaf chain per output
-#pragma unroll
-      for (int kk = 0; kk < BK / 2; ++kk) {
-        float af[RM], bfr[RN];
-#pragma unroll
-        for (int i = 0; i < RM; ++i) af[i] = LA::frag32(abuf, wm0 + i * 32, kk, lane);
-#pragma unroll
-        for (int j = 0; j < RN; ++j) bfr[j] = LB::frag32(bbuf, wn0 + j * 32, kk, lane);
-#pragma unroll
-        for (int i = 0; i < RM; ++i)
-#pragma unroll
-          for (int j = 0; j < RN; ++j) acc[i][j] = mfma32_f32(af[i], bfr[j], acc[i][j]);
-      }
-    }
-    if (more) {
-      char* nbuf = smem + (cur ^ 1) * STAGE;
-      LA::store(nbuf, tid, ra);
-      LB::store(nbuf + LA::BYTES, tid, rb);
-    }
-    __syncthreads();
-  }
-
-  igemm_epilogue<T, CFG>(acc, ep, rm, smem, M, N, m0, n0, tid, lane, wave, wm0, wn0);
-}
-
-#endif  // CLITE_DIAG
 
 }  // namespace clite
 #endif  // CLITE_IGEMM_H

@@ -1,4 +1,4 @@
-// LDS-DMA pipelined variant of the implicit-GEMM engine (same math, operands, epilogue and C ABI as igemm.h).
+// Operand loaders and main loops of the implicit-GEMM engine (geometry, tile configuration and epilogues: igemm.h).
 //
 // Operand tiles go global -> LDS with `buffer_load_dwordx4 ... lds` (no VGPR staging, no ds_write), three LDS stages, one raw
 // s_barrier per K tile and a counted `s_waitcnt vmcnt(N)` that leaves the next tile's loads in flight across the barrier:
@@ -9,6 +9,7 @@
 //             issue(t+2 -> buf (t+2)%3)  // overwrites the buffer of tile t-1
 //             compute(buf t%3)
 //
+// Out-of-range source offsets (OOB_OFF) read as zero, which implements im2col padding, ragged tile edges and K tails without branches.
 // The DMA destination is lane-linear (wave-uniform base + lane*16 B), so rows cannot be padded; bank conflicts are removed by
 // an XOR swizzle applied to the SOURCE chunk each lane fetches and to the fragment read address (the same involution on both
 // sides):
@@ -45,6 +46,7 @@ struct DmaKC {
   static constexpr int EPC = 16 / (int)sizeof(T);
   static constexpr int NI = ROWS / 64;               // DMA instructions per wave per tile (4 waves x 16 rows each)
   static constexpr int BYTES = ROWS * 64;
+  static constexpr bool XC = false;
   const void* ptr;
   uint32_t bytes;
   ConvGeom g;
@@ -154,6 +156,7 @@ struct DmaXCStrided {
   static constexpr int RPI = 64 / CPR;                       // k-rows per wave instruction
   static constexpr int NI = BK / (NW * RPI);                 // instructions per wave per tile
   static constexpr int BYTES = BK * ROWB;
+  static constexpr bool XC = true;
   static_assert(CPR <= 64 && 64 % CPR == 0 && BK % (NW * RPI) == 0 && NI >= 1, "tile shape");
   const void* ptr;
   uint32_t bytes;
@@ -229,6 +232,7 @@ template <typename T, int COLS, int BK, int NW = 4>
 struct DmaXCGather {
   typedef DmaXCStrided<T, COLS, BK, NW> L;
   static constexpr int EPC = L::EPC, ROWB = L::ROWB, CPR = L::CPR, RPI = L::RPI, NI = L::NI, BYTES = L::BYTES;
+  static constexpr bool XC = true;
   const void* ptr;
   uint32_t bytes;
   ConvGeom g;
@@ -509,8 +513,8 @@ DEV int fp8_frag_off64(int x0, int half, int lane) {
 // staged once per workgroup behind the operand ring. A lane's fragment holds 8 consecutive k of one row, so each k-step reads 8 + 8 coefficients (two
 // half-wave broadcast reads each).
 template <typename T, class CFG, class LA, class LB, int FORM = 0, bool SPLIT = false, bool F8 = false, bool AFF = false>
-__global__ __launch_bounds__(256, (FORM && CLITE_BN_HALF) ? 3 : 2) void igemm_dma_bn_kernel(LA la, LB lb, Epilogue ep, RowMap rm, int M, int N, int ktiles, int rows_per_wg,
-                                                                                            const float* f8_a, const float* f8_b) {
+__global__ __launch_bounds__(256, 2) void igemm_dma_bn_kernel(LA la, LB lb, Epilogue ep, RowMap rm, int M, int N, int ktiles, int rows_per_wg,
+                                                              const float* f8_a, const float* f8_b) {
   constexpr int BM = CFG::BM, BN = CFG::BN, BK = CFG::BK;
   constexpr int RM = CFG::RM, RN = CFG::RN;
 #ifndef CLITE_BN_STAGES
@@ -518,7 +522,7 @@ __global__ __launch_bounds__(256, (FORM && CLITE_BN_HALF) ? 3 : 2) void igemm_dm
 #endif
   constexpr int NSTAGE = CLITE_BN_STAGES;
   constexpr int STAGE = LA::BYTES + LB::BYTES;
-  constexpr int EPIB = (CFG::BM / ((FORM && CLITE_BN_HALF) ? 2 : 1)) * CFG::EPI_PITCH;      // the epilogue stages the whole tile, or half of it at a time (igemm_epilogue_bn NP)
+  constexpr int EPIB = CFG::BM * CFG::EPI_PITCH;      // the epilogue stages the whole tile
   constexpr int RED = (256 / (CFG::BN / 8)) * (CFG::BN / 8) * 16 * 4;      // bn_epi_finish's fold image
   constexpr int SMEM0 = (NSTAGE * STAGE > EPIB) ? NSTAGE * STAGE : EPIB;
   constexpr int SMEM1 = SMEM0 > RED ? SMEM0 : RED;
@@ -579,8 +583,8 @@ __global__ __launch_bounds__(256, (FORM && CLITE_BN_HALF) ? 3 : 2) void igemm_dm
   BnEpiState est;
   bn_epi_begin<CFG>(est, ep, N, n0, tid);
   PHASE(0);          // launch prologue: addresses, BatchNorm means
-  // rows of epilogue operands requested ahead of the tile's main loop (BnRows): the specialised forms with whole-tile staging
-  constexpr int EARLY = (FORM && !CLITE_BN_HALF && sizeof(T) == 2) ? (CLITE_BN_EARLY < BnRows<T, CFG, FORM>::ROWS_PT ? CLITE_BN_EARLY : BnRows<T, CFG, FORM>::ROWS_PT) : 0;
+  // rows of epilogue operands requested ahead of the tile's main loop (BnRows): the specialised forms
+  constexpr int EARLY = (FORM && sizeof(T) == 2) ? (CLITE_BN_EARLY < BnRows<T, CFG, FORM>::ROWS_PT ? CLITE_BN_EARLY : BnRows<T, CFG, FORM>::ROWS_PT) : 0;
   for (int m0 = row_begin; m0 < row_end; m0 += BM) {
     BnRows<T, CFG, FORM> rows;
 #pragma unroll

@@ -359,7 +359,6 @@ def jsd_backward(rt, mod, saved, gout):
     dtxt = prior_backward(rt, mod.text_prior_d, pctx_t, gout, mod.prior_weight, None) if pctx_t is not None else None
     dimg = mi_block_backward(rt, gd.img_block, c1, df1, dimg)
     dtxt = mi_block_backward(rt, gd.text_block, c2, df2, dtxt)
-    rt.join_aux()
     rt.grads_ready(mod)
     return dimg, dtxt
 
@@ -588,7 +587,6 @@ def jsd_general_backward(rt, mod, saved, gout):
         dimg = prior_backward(rt, mod.prior_d, pctx_i, gout, mod.prior_weight, dimg.contiguous())
     if pctx_t is not None:
         dtxt = prior_backward(rt, mod.text_prior_d, pctx_t, gout, mod.prior_weight, dtxt.contiguous())
-    rt.join_aux()
     rt.grads_ready(mod)
     return dimg, dtxt, dnimg, dntxt, daimg, datxt
 

@@ -353,7 +353,7 @@ def resnet_backward(rt, net, ctx, dfeat, defer=None, stop_block=0, resume=False)
     blocks = list(net.blocks())
     recs = ctx["recs"]
     own_group = None
-    if defer is None and rt.group_wgrad and not rt.overlap_wgrad and not rt._capturing:      # (a capture cannot allocate the pinned staging)
+    if defer is None and rt.group_wgrad and not rt._capturing:      # (a capture cannot allocate the pinned staging)
         # uncaptured (eager / autograd) backward: the same grouped launch, issued at the end of this call on the same stream
         defer = own_group = hip.WgradGroup(rt.dt)
     staged = own_group is not None and getattr(rt, "exchange", None) is not None
@@ -366,7 +366,7 @@ def resnet_backward(rt, net, ctx, dfeat, defer=None, stop_block=0, resume=False)
         dw = rt.arena.g(u_.conv.weight)
         cv_ = u_.cv
         if defer is None:
-            rt.aux_launch(lambda: hip.conv_wgrad(dy_, u_.x, cv_, dw), dy_)
+            hip.conv_wgrad(dy_, u_.x, cv_, dw)
         elif (f8 is not None and rt.fp8_wgrad and dy8_ is not None and u_.x8 is not None and cv_.K >= 256 and cv_.R * cv_.S * cv_.C >= 256
               and cv_.K % 16 == 0 and cv_.C % 16 == 0):
             # both operands exist in fp8 already (x: e4m3, written by the bn_apply in front for the fp8 forward; dy: e5m2, written by bn_bwd_apply for the
@@ -572,6 +572,5 @@ def resnet_backward(rt, net, ctx, dfeat, defer=None, stop_block=0, resume=False)
         else:
             rt.grads_ready(net)       # every gradient of the encoder became final with that launch
     elif defer is None:
-        rt.join_aux()
         rt.grads_ready(net.conv1)
         rt.grads_ready(net.bn1)

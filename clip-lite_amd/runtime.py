@@ -324,10 +324,10 @@ class DeviceRuntime:
         self.fp8_dgrad = False             # ... and the input gradients of the image encoder's 3 x 3 (>= 128 channels) / late 1 x 1 convs inside a block: e5m2 gradient x e4m3
                                            # transposed weights (clite_conv_dgrad_fp8), the gradient quantised by the producing bn_bwd_apply (needs fp8 = True)
         self.fp8_nets = {}                 # id(ResNet) -> fp8.Fp8Forward
-        self.group_wgrad = bool(lowp)      # weight gradients of a backward pass as grouped launches (hip.WgradGroup / clite_wgrad_group)
+        self.group_wgrad = bool(lowp)      # weight gradients of a backward pass as grouped launches (hip.WgradGroup / clite_wgrad_group); otherwise in line
+                                           # on the launching stream - measured on MI355X, a forked weight-gradient stream slowed the step, 25.1 -> 28.6 ms
         if lowp and self.device.type == "cuda":
             hip.patch_workspace(self.device)          # scratch of the patch-resident 3 x 3 weight gradient: must exist before any stream capture
-        self._aux_streams, self._aux_busy, self._aux_keep, self.overlap_wgrad = {}, set(), {}, False
         self.steps = 0
         self.seed_dev, self._capturing, self._slots, self.graph_slots, self._graph_next = None, False, 0, 0, -1
         # flatten num_batches_tracked buffers per top-level owner
@@ -375,55 +375,12 @@ class DeviceRuntime:
             R = 1 if rows <= 65536 else 2 if rows <= 262144 else 4
         return hip.Stats(self.zpool.take(R * 3 * Cc), R, Cc)
 
-    # -- weight gradients off the critical path ---------------------------------------------------------------------------
-    # In backward only dgrad -> BN backward -> dgrad ... is a dependency chain; every weight-gradient GEMM (conv wgrad, linear
-    # dW/db) just needs dy and the saved input and feeds nothing but the gradient arena. They are enqueued on an auxiliary stream
-    # so they can fill the CUs that the chain's small-grid / latency-bound kernels leave idle (in a captured step: parallel
-    # branches of the hipGraph). `join_aux` orders the caller's stream after them. OFF by default (`overlap_wgrad`): measured on
-    # MI355X at batch 128 with the text encoder already running beside the ResNet, the extra branch slows the step (25.1 ->
-    # 28.6 ms): the split-K wgrad grids contend with the dgrad/BN chain instead of filling gaps.
-    def aux_launch(self, fn, *tensors):
-        if self.device.type != "cuda" or not self.overlap_wgrad:
-            fn()
-            return
-        cur = torch.cuda.current_stream(self.device)
-        if self.side_stream is not None and cur == self.side_stream:
-            # the text encoder's stream is itself a forked branch; forking a second level from it makes hipStreamEndCapture
-            # crash (ROCm 7.2), and BERT's backward is not the critical path of the step anyway: keep its dW GEMMs in line
-            fn()
-            return
-        st = self._aux_for(cur)
-        st.wait_stream(cur)
-        with torch.cuda.stream(st):
-            fn()
-        # transient operands (dy) must not be recycled by the allocator before the aux stream has read them: keep them referenced
-        # until join_aux has ordered the launching stream after the aux stream
-        self._aux_keep.setdefault(cur.cuda_stream, []).extend(t for t in tensors if t is not None)
-        self._aux_busy.add(cur.cuda_stream)
-
-    def _aux_for(self, cur):
-        """The auxiliary stream (created outside any capture: begin_capture calls this first)."""
-        st = self._aux_streams.get("main")
-        if st is None:
-            st = self._aux_streams["main"] = torch.cuda.Stream(device=self.device)
-        return st
-
-    def join_aux(self):
-        if self.device.type != "cuda":
-            return
-        cur = torch.cuda.current_stream(self.device)
-        if cur.cuda_stream in self._aux_busy:
-            cur.wait_stream(self._aux_for(cur))
-            self._aux_busy.discard(cur.cuda_stream)
-            self._aux_keep.pop(cur.cuda_stream, None)
-
     def grads_ready(self, module):
         """Tell the gradient exchange (data parallel) that every parameter gradient under `module` is final for this step,
         so its region of the flat gradient arena can be all-reduced while the rest of backward still runs."""
         ex = getattr(self, "exchange", None)
         if ex is None:
             return
-        self.join_aux()          # the region's weight gradients were written on the auxiliary stream
         span = self._spans.get(id(module))
         if span is None:
             offs = [self.arena.index[p._clite[1]] for p in module.parameters() if hasattr(p, "_clite")]
@@ -462,7 +419,6 @@ class DeviceRuntime:
             self.seed_dev = torch.zeros(self.SEED_SLOTS, device=self.device, dtype=torch.int64)
         if self.side_stream is None:
             self.side_stream = self.new_side_stream()
-        self._aux_for(torch.cuda.current_stream(self.device))
         self._capturing, self._slots = True, 0
         self._saved_zpools, self._zpools = self._zpools, {}     # chunks taken during capture live in the graph's memory pool
 

@@ -1,6 +1,6 @@
 """A/B timing of executor switches on the captured train step: python tools/ab_runtime.py [attr=value ...] [--steps 50]
 `text.attr=value` sets an attribute of the BERT module (dropout probabilities), `hip.path=value` one of clip_lite_amd.hip, `step.attr=value` one of the
-TrainStep. Each other `attr=value` sets an attribute of the model's DeviceRuntime (fuse_bn_backward, s2_classes, group_wgrad, overlap_wgrad ...) before the
+TrainStep. Each other `attr=value` sets an attribute of the model's DeviceRuntime (fuse_bn_backward, s2_classes, group_wgrad ...) before the
 step is captured; prints ms/step (HIP events around `steps` replays). The baseline is the same command without arguments."""
 import argparse
 import contextlib
