@@ -35,6 +35,26 @@ ConvGeom geom_dense(int rows, int K, int ld = 0) {  // [rows][K] (row stride ld)
   return g;
 }
 
+// an R x S window (stride, padding padh / padw) over N images [H][W] of C channels, `px` elements from one pixel to the next, whose positions form the
+// [N][RH][RW] row grid
+ConvGeom geom_window(int N, int H, int W, int C, int px, int RH, int RW, int R, int S, int stride, int padh, int padw) {
+  ConvGeom g;
+  g.H = H; g.W = W; g.C = C;
+  g.sN = H * W * px; g.sH = W * px; g.sW = px;
+  g.RH = RH; g.RW = RW; g.R = R; g.S = S; g.stride = stride; g.pad = padh; g.padw = padw;
+  g.rows = N * RH * RW; g.concat = 0;
+  g.div_hw = fastdiv_make(RH * RW);
+  g.div_w = fastdiv_make(RW);
+  return g;
+}
+// GEMM row r = pixel (n, gh, gw) of an [N][GH][GW] grid <-> pixel (n, gh*stride + off_h, gw*stride + off_w) of the [N][H][W] tensor (on = 1: output rows
+// scattered there; 2: the residual's rows gathered from the compact grid, subsampled_row)
+RowMap row_map(int on, int GH, int GW, int H, int W, int stride, int off_h = 0, int off_w = 0) {
+  RowMap rm;
+  rm.on = on; rm.div_hw = fastdiv_make(GH * GW); rm.div_w = fastdiv_make(GW); rm.H = H; rm.W = W; rm.stride = stride; rm.off_h = off_h; rm.off_w = off_w;
+  return rm;
+}
+
 bool fits32(size_t elems, size_t esize) { return elems * esize < 0xF0000000ull; }
 
 template <typename T> struct Cfg {
@@ -44,6 +64,14 @@ template <typename T> struct Cfg {
   typedef TileCfg<64, 128, BK, 64, 32> C64x128;     // weight gradients of convs with <= 64 output channels
   typedef TileCfg<128, 64, BK, 32, 64> C128x64;     // ... or <= 64 (r, s, ci) columns
 };
+// The tile by output columns: 256 x 64 for at most 64 of them (a 128-column tile would be half empty), 128 x 128 otherwise. f receives a Tile, which names
+// the configuration and the row / column counts its two loaders take.
+template <class C> struct Tile { typedef C CFG; static constexpr int ROWS = C::BM, COLS = C::BN; };
+template <typename T, class F> int with_cols(int cols, F f) {
+  return cols <= 64 ? f(Tile<typename Cfg<T>::C256x64>{}) : f(Tile<typename Cfg<T>::C128>{});
+}
+// f(T{}) for the element type T that dtype names (the entry points' check_* functions admit no third one)
+template <class F> int with_dtype(int dtype, F f) { return dtype == CLITE_BF16 ? f(bf16{}) : f(float{}); }
 
 // Kernel-selection knobs. The product library has none: every choice below is a fixed function of the problem shape. A diagnostic build
 // (-DCLITE_DIAG=1, tools/README.md) reads them from the environment for A/B timing.
@@ -154,136 +182,186 @@ extern "C" void clite_probe_set_affine(const float* scale, const float* shift) {
 #endif
 bool f32_split() { return g_f32_split.load(std::memory_order_relaxed) != 0; }
 
-template <typename T, class CFG, class LA, class LB>
-int launch(const LA& la, const LB& lb, const clite_epilogue& ep, int M, int N, int Ktot, int splits, hipStream_t st, RowMap rm = RowMap{}) {
-  if (deterministic()) {
-    if (ep.colsum) {       // statistics from the stored tensor, one contribution per address (colstats_det_kernel)
-      clite_epilogue e2 = ep;
-      e2.colsum = nullptr;
-      int rc = launch<T, CFG>(la, lb, e2, M, N, Ktot, splits, st, rm);
-      return rc ? rc : colstats_det<T>(ep, rm, M, N, st);
-    }
-    splits = 1;            // one workgroup per output tile over the whole K range: a single add per address
-  }
-  if constexpr (sizeof(T) == 2 && std::is_same<CFG, typename Cfg<T>::C128>::value) {
-    // bf16, 128-column-or-wider outputs: the wide-K 8-wave kernels (igemm_wide.h) where the shape allows
-    const int rcw = launch_wide(wide_op(la), wide_op(lb), ep, rm, M, N, Ktot, splits, st);
-    if (rcw != WIDE_NOT_TAKEN) return rcw;
-  }
-  int ktiles = (Ktot + CFG::BK - 1) / CFG::BK;
+// ---- launch(): one GEMM on the kernel that its shape and epilogue select. Each step either launches and returns the code (-1: refused) or is DECLINED.
+constexpr int DECLINED = WIDE_NOT_TAKEN;
+
+// rejects what the BatchNorm-backward instantiation does not do: exactly out = [(alpha*acc) (* relu'(aux))] (+ residual) [(* relu'(aux))], colsum; nothing else
+bool bn_dgrad_rejects(const clite_epilogue& ep, int splits) {
+  return ep.atomic || ep.act || ep.preact || ep.drop_p > 0.f || (ep.dact_aux && ep.dact != 1) || (ep.dact_aux && ep.relu_bits) || splits != 1;
+}
+// admits the bf16 store of the bare accumulator (+ column statistics) — no bias, no scale — that FORM 4 of the row-range kernel does
+bool ep_bare_store(const clite_epilogue& ep) {
+  return !ep.atomic && !ep.out_f32 && !ep.preact && ep.act == CLITE_ACT_NONE && !ep.dact_aux && ep.drop_p <= 0.f && !ep.residual && !ep.bias && ep.alpha == 1.f &&
+         !ep.relu_bits && !ep.splitk_ws;
+}
+// admits the plain bf16 store (+ bias, + scale, + column statistics) of the branch-free epilogue instantiation (EPI 2)
+bool ep_plain_store(const clite_epilogue& ep) {
+  return !ep.atomic && !ep.out_f32 && !ep.preact && ep.act == CLITE_ACT_NONE && !ep.dact_aux && ep.drop_p <= 0.f && !ep.residual && !ep.bn_y && !ep.mask_after_residual;
+}
+// admits what splitk_finish_kernel applies to the workspace: everything but float atomics, dropout and the BatchNorm-backward form
+bool ep_splitk_finishable(const clite_epilogue& ep) { return ep.splitk_ws && !ep.atomic && !(ep.drop_p > 0.f) && !ep.bn_y && !ep.mask_after_residual; }
+
+// K range of a launch cut into `splits` equal runs of K tiles, and its grid
+struct KSplit { int ktiles, splits, per, tiles, xsplits; dim3 grid; };
+template <class CFG> KSplit ksplit(int M, int N, int Ktot, int splits) {
+  KSplit k;
+  k.ktiles = (Ktot + CFG::BK - 1) / CFG::BK;
   if (splits < 1) splits = 1;
-  if (splits > ktiles) splits = ktiles;
-  int per = (ktiles + splits - 1) / splits;
-  splits = (ktiles + per - 1) / per;
-  int tiles = ((M + CFG::BM - 1) / CFG::BM) * ((N + CFG::BN - 1) / CFG::BN);
+  if (splits > k.ktiles) splits = k.ktiles;
+  k.per = (k.ktiles + splits - 1) / splits;
+  k.splits = (k.ktiles + k.per - 1) / k.per;
+  k.tiles = ((M + CFG::BM - 1) / CFG::BM) * ((N + CFG::BN - 1) / CFG::BN);
   // >= 8 K splits: 1-D grid in which each XCD owns whole splits (igemm_dma.h)
-  const int xsplits = (xcd_split_pref() && splits >= 8) ? splits : 0;
-  const dim3 grid = xsplits ? dim3(8 * ((splits + 7) / 8) * tiles, 1, 1) : dim3(tiles, 1, splits);
-  // a grid that gives each CU at most ~2 workgroups hides DMA latency with a deeper ring instead (4 stages x 16 KB = 64 KB)
-  constexpr int STAGE = LA::BYTES + LB::BYTES;
-  if (ep.bn_y || ep.mask_after_residual) {     // BatchNorm-backward epilogue: its own (register-heavier) instantiation, dgrad loaders only
-    // it implements exactly: out = [(alpha*acc) (* relu'(aux))] (+ residual) [(* relu'(aux))], colsum; nothing else
-    if (ep.atomic || ep.act || ep.preact || ep.drop_p > 0.f || (ep.dact_aux && ep.dact != 1) || (ep.dact_aux && ep.relu_bits) || splits != 1) return -1;
-    if constexpr (IsDgrad<LA>::value) {
-      // the two forms of the bf16 ResNet backward get their own instantiations (igemm_epilogue_bn's FORM); everything else the run-time form
-      constexpr bool kc_b = !LB::XC;
-      int form = 0;
-      if (sizeof(T) == 2 && kc_b && ep.relu_bits && ep.bn_y && !ep.dact_aux && !ep.out_f32 && ep.alpha == 1.f) {
-        if (!ep.residual && !ep.mask_after_residual) form = ep.bias ? 5 : 1;
-        else if (ep.residual && ep.mask_after_residual) form = rm.on == 2 ? 3 : 2;
-      }
-      // row-range persistent form (igemm_dma_bn_kernel) for the short-K (1 x 1) dgrads whose tile count exceeds the resident slots (two
-      // workgroups per CU); one tile per workgroup otherwise
-      const int slots = CLITE_BN_SLOTS;
-      const int tiles_n = (N + CFG::BN - 1) / CFG::BN, tiles_m = (M + CFG::BM - 1) / CFG::BM;
-      int rows_per_wg = CFG::BM, slices = tiles_m;
-      if ((la.g.R * la.g.S == 1 || la.g.concat) && (long)tiles_m * tiles_n > slots && tiles_n <= slots && !deterministic()) {
-        slices = slots / tiles_n;
-        rows_per_wg = ((M + slices - 1) / slices + 7) & ~7;
-        if (rows_per_wg < CFG::BM) rows_per_wg = CFG::BM;
-        slices = (M + rows_per_wg - 1) / rows_per_wg;
-      }
-      const dim3 g(slices * tiles_n);
-      if constexpr (sizeof(T) == 2 && kc_b) {
-        if (form == 1) hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, LA, LB, 1>), g, dim3(256), 0, st, la, lb, ep, rm, M, N, ktiles, rows_per_wg, nullptr, nullptr);
-        else if (form == 2) hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, LA, LB, 2>), g, dim3(256), 0, st, la, lb, ep, rm, M, N, ktiles, rows_per_wg, nullptr, nullptr);
-        else if (form == 3) hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, LA, LB, 3>), g, dim3(256), 0, st, la, lb, ep, rm, M, N, ktiles, rows_per_wg, nullptr, nullptr);
-        else if (form == 5) hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, LA, LB, 5>), g, dim3(256), 0, st, la, lb, ep, rm, M, N, ktiles, rows_per_wg, nullptr, nullptr);
-        else hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, LA, LB, 0>), g, dim3(256), 0, st, la, lb, ep, rm, M, N, ktiles, rows_per_wg, nullptr, nullptr);
-      } else {
-        bool done = false;
-        if constexpr (sizeof(T) == 4) {
-          if (f32_split()) {
-            hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, LA, LB, 0, true>), g, dim3(256), 0, st, la, lb, ep, rm, M, N, ktiles, rows_per_wg, nullptr, nullptr);
-            done = true;
-          }
-        }
-        if (!done)
-          hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, LA, LB, 0>), g, dim3(256), 0, st, la, lb, ep, rm, M, N, ktiles, rows_per_wg, nullptr, nullptr);
-      }
-      return (int)hipGetLastError();
-    } else {
-      return -1;
-    }
+  k.xsplits = (xcd_split_pref() && k.splits >= 8) ? k.splits : 0;
+  k.grid = k.xsplits ? dim3(8 * ((k.splits + 7) / 8) * k.tiles, 1, 1) : dim3(k.tiles, 1, k.splits);
+  return k;
+}
+
+// The row-range persistent form (igemm_dma_bn_kernel): CLITE_BN_SLOTS workgroups, each walking its range of rows (a multiple of 8, >= one tile) of one column tile
+struct RowSlices { int slices, rows_per_wg; };
+RowSlices row_slices(int M, int tiles_n, int BM) {
+  RowSlices r;
+  r.slices = CLITE_BN_SLOTS / tiles_n;
+  r.rows_per_wg = ((M + r.slices - 1) / r.slices + 7) & ~7;
+  if (r.rows_per_wg < BM) r.rows_per_wg = BM;
+  r.slices = (M + r.rows_per_wg - 1) / r.rows_per_wg;
+  return r;
+}
+
+// f(std::integral_constant<int, F>) for the F among FORMS that equals form; the last of FORMS serves every other value
+template <int F, int... REST, class Fn> void with_form(int form, Fn f) {
+  if constexpr (sizeof...(REST) > 0) {
+    if (form != F) return with_form<REST...>(form, f);
   }
-  // The HBM-bound 1 x 1 FORWARD convolutions of the 56 x 56 / 28 x 28 stages (K <= 512, thousands of tiles, plain bf16 store + column statistics:
-  // 3.4 - 3.8 TB/s as one tile per workgroup) in the row-range persistent structure of the BatchNorm-backward dgrads, which
-  // sustains 5.2 TB/s on the same tensors (igemm_epilogue_bn FORM 4: no operands, sums of v and v^2): every workgroup is resident at once, walks
-  // its own row range of one column tile and adds its column sums once.
+  f(std::integral_constant<int, F>{});
+}
+
+template <typename T, class CFG, class LA, class LB>
+int launch(const LA& la, const LB& lb, const clite_epilogue& ep, int M, int N, int Ktot, int splits, hipStream_t st, RowMap rm = RowMap{});
+
+// deterministic mode (det.h). Declines, with the K splits taken away, when the launch accumulates no statistics
+template <typename T, class CFG, class LA, class LB>
+int launch_deterministic(const LA& la, const LB& lb, const clite_epilogue& ep, int M, int N, int Ktot, int& splits, hipStream_t st, const RowMap& rm) {
+  if (!deterministic()) return DECLINED;
+  if (ep.colsum) {       // statistics from the stored tensor, one contribution per address (colstats_det_kernel)
+    clite_epilogue e2 = ep;
+    e2.colsum = nullptr;
+    int rc = launch<T, CFG>(la, lb, e2, M, N, Ktot, splits, st, rm);
+    return rc ? rc : colstats_det<T>(ep, rm, M, N, st);
+  }
+  splits = 1;            // one workgroup per output tile over the whole K range: a single add per address
+  return DECLINED;
+}
+
+// bf16, 128-column-or-wider outputs: the wide-K 8-wave kernels (igemm_wide.h) where the shape allows
+template <typename T, class CFG, class LA, class LB>
+int launch_on_wide(const LA& la, const LB& lb, const clite_epilogue& ep, const RowMap& rm, int M, int N, int Ktot, int splits, hipStream_t st) {
+  if constexpr (sizeof(T) == 2 && std::is_same<CFG, typename Cfg<T>::C128>::value) return launch_wide(wide_op(la), wide_op(lb), ep, rm, M, N, Ktot, splits, st);
+  else return DECLINED;
+}
+
+// BatchNorm-backward epilogue (ep.bn_y || ep.mask_after_residual): its own (register-heavier) instantiation, dgrad loaders only. Never declines
+template <typename T, class CFG, class LA, class LB>
+int launch_bn_dgrad(const LA& la, const LB& lb, const clite_epilogue& ep, const RowMap& rm, int M, int N, int ktiles, int splits, hipStream_t st) {
+  if (bn_dgrad_rejects(ep, splits)) return -1;
+  if constexpr (!IsDgrad<LA>::value) {
+    return -1;
+  } else {
+    // the forms of the bf16 ResNet backward get their own instantiations (igemm_epilogue_bn's FORM); everything else the run-time form
+    constexpr bool kc_b = !LB::XC;
+    int form = 0;
+    if (sizeof(T) == 2 && kc_b && ep.relu_bits && ep.bn_y && !ep.dact_aux && !ep.out_f32 && ep.alpha == 1.f) {
+      if (!ep.residual && !ep.mask_after_residual) form = ep.bias ? 5 : 1;
+      else if (ep.residual && ep.mask_after_residual) form = rm.on == 2 ? 3 : 2;
+    }
+    // row-range persistent form for the short-K (1 x 1) dgrads whose tile count exceeds the resident slots (two workgroups per CU); one tile per
+    // workgroup otherwise
+    const int tiles_n = (N + CFG::BN - 1) / CFG::BN, tiles_m = (M + CFG::BM - 1) / CFG::BM;
+    RowSlices r{tiles_m, CFG::BM};
+    if ((la.g.R * la.g.S == 1 || la.g.concat) && (long)tiles_m * tiles_n > CLITE_BN_SLOTS && tiles_n <= CLITE_BN_SLOTS && !deterministic())
+      r = row_slices(M, tiles_n, CFG::BM);
+    auto go = [&](auto form_c, auto split_c) {
+      hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, LA, LB, decltype(form_c)::value, decltype(split_c)::value>), dim3(r.slices * tiles_n), dim3(256), 0, st, la, lb,
+                         ep, rm, M, N, ktiles, r.rows_per_wg, nullptr, nullptr);
+    };
+    if constexpr (sizeof(T) == 2 && kc_b) {
+      with_form<1, 2, 3, 5, 0>(form, [&](auto form_c) { go(form_c, std::false_type{}); });
+    } else if constexpr (sizeof(T) == 4) {      // f32 storage: three bf16 MFMAs per product under clite_set_f32_split
+      if (f32_split()) go(std::integral_constant<int, 0>{}, std::true_type{});
+      else go(std::integral_constant<int, 0>{}, std::false_type{});
+    } else {
+      go(std::integral_constant<int, 0>{}, std::false_type{});
+    }
+    return (int)hipGetLastError();
+  }
+}
+
+// The HBM-bound 1 x 1 FORWARD convolutions of the 56 x 56 / 28 x 28 stages (K <= 512, thousands of tiles, plain bf16 store + column statistics:
+// 3.4 - 3.8 TB/s as one tile per workgroup) in the row-range persistent structure of the BatchNorm-backward dgrads, which
+// sustains 5.2 TB/s on the same tensors (igemm_epilogue_bn FORM 4: no operands, sums of v and v^2): every workgroup is resident at once, walks
+// its own row range of one column tile and adds its column sums once.
+template <typename T, class CFG, class LA, class LB>
+int launch_persistent_fwd(const LA& la, const LB& lb, const clite_epilogue& ep, const RowMap& rm, int M, int N, const KSplit& k, hipStream_t st) {
 #ifndef CLITE_NO_PERSIST_FWD
   if constexpr (sizeof(T) == 2 && !LA::XC && !LB::XC && !IsDgrad<LA>::value) {
-    const bool plain_fwd = !ep.atomic && !ep.out_f32 && !ep.preact && ep.act == CLITE_ACT_NONE && !ep.dact_aux && ep.drop_p <= 0.f && !ep.residual && !ep.bias &&
-                           ep.alpha == 1.f && !ep.relu_bits && !ep.splitk_ws && splits == 1 && rm.on == 0;
     const int tiles_n = (N + CFG::BN - 1) / CFG::BN, tiles_m = (M + CFG::BM - 1) / CFG::BM;
-    if (plain_fwd && la.g.R * la.g.S == 1 && ktiles <= 16 && (long)tiles_m * tiles_n > 2 * CLITE_BN_SLOTS && tiles_n <= CLITE_BN_SLOTS && !deterministic() &&
-        tile_policy_value() == 0) {
-      int slices = CLITE_BN_SLOTS / tiles_n;
-      int rows_per_wg = ((M + slices - 1) / slices + 7) & ~7;
-      if (rows_per_wg < CFG::BM) rows_per_wg = CFG::BM;
-      slices = (M + rows_per_wg - 1) / rows_per_wg;
+    if (ep_bare_store(ep) && k.splits == 1 && rm.on == 0 && la.g.R * la.g.S == 1 && k.ktiles <= 16 && (long)tiles_m * tiles_n > 2 * CLITE_BN_SLOTS &&
+        tiles_n <= CLITE_BN_SLOTS && !deterministic() && tile_policy_value() == 0) {
+      const RowSlices r = row_slices(M, tiles_n, CFG::BM);
 #ifdef CLITE_PROBE_AFRAG
-      if (g_probe_aff[0] && ktiles * CFG::BK <= 512) {
-        hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, LA, LB, 4, false, false, true>), dim3(slices * tiles_n), dim3(256), 0, st, la, lb, ep,
-                           rm, M, N, ktiles, rows_per_wg, g_probe_aff[0], g_probe_aff[1]);
+      if (g_probe_aff[0] && k.ktiles * CFG::BK <= 512) {
+        hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, LA, LB, 4, false, false, true>), dim3(r.slices * tiles_n), dim3(256), 0, st, la, lb, ep,
+                           rm, M, N, k.ktiles, r.rows_per_wg, g_probe_aff[0], g_probe_aff[1]);
         return (int)hipGetLastError();
       }
 #endif
-      hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, LA, LB, 4>), dim3(slices * tiles_n), dim3(256), 0, st, la, lb, ep, rm, M, N, ktiles,
-                         rows_per_wg, nullptr, nullptr);
+      hipLaunchKernelGGL((igemm_dma_bn_kernel<T, CFG, LA, LB, 4>), dim3(r.slices * tiles_n), dim3(256), 0, st, la, lb, ep, rm, M, N, k.ktiles,
+                         r.rows_per_wg, nullptr, nullptr);
       return (int)hipGetLastError();
     }
   }
 #endif
+  return DECLINED;
+}
+
+// one tile per workgroup: the two-K-group kernel, or the DMA ring at 4 or 3 stages with the generic or the plain-store epilogue. Never declines
+template <typename T, class CFG, class LA, class LB>
+int launch_ring(const LA& la, const LB& lb, const clite_epilogue& ep, const RowMap& rm, int M, int N, const KSplit& k, hipStream_t st) {
+  constexpr int STAGE = LA::BYTES + LB::BYTES;
   // at most one workgroup per CU: two K-groups per workgroup (8 waves, in-workgroup split-K) instead of one wave per SIMD. bf16 only:
   // the exact-f32 parity mode keeps one k-ordered fmaf chain per output, which is what tracks the CPU reference most closely
-  if (g2_pref() != 0 && 6 * STAGE <= 160 * 1024 && (((long)tiles * splits <= 256 && per >= 8 && sizeof(T) == 2) || g2_pref() == 2)) {
+  if (g2_pref() != 0 && 6 * STAGE <= 160 * 1024 && (((long)k.tiles * k.splits <= 256 && k.per >= 8 && sizeof(T) == 2) || g2_pref() == 2)) {
     // (4- and 5-stage rings for this kernel were measured and dropped: 38.6 / 39.6 / 42.6 us on the N = 768 BERT shapes)
-    hipLaunchKernelGGL((igemm_dma_kernel_g2<T, CFG, LA, LB, 3>), grid, dim3(512), 0, st, la, lb, ep, rm,
-                       M, N, ktiles, per, xsplits);
+    hipLaunchKernelGGL((igemm_dma_kernel_g2<T, CFG, LA, LB, 3>), k.grid, dim3(512), 0, st, la, lb, ep, rm, M, N, k.ktiles, k.per, k.xsplits);
     return (int)hipGetLastError();
   }
+  // a grid that gives each CU at most ~2 workgroups hides DMA latency with a deeper ring instead (4 stages x 16 KB = 64 KB)
+  const bool deep = 4 * STAGE <= 65536 && (long)k.tiles * k.splits <= 2 * 256 && k.per >= 4;
   if constexpr (sizeof(T) == 4) {
     if (f32_split()) {          // f32 storage, three bf16 MFMAs per product (clite_set_f32_split)
-      if (4 * STAGE <= 65536 && (long)tiles * splits <= 2 * 256 && per >= 4)
-        hipLaunchKernelGGL((igemm_dma_kernel<T, CFG, LA, LB, 4, 0, true>), grid, dim3(256), 0, st, la, lb, ep, rm, M, N, ktiles, per, xsplits);
-      else
-        hipLaunchKernelGGL((igemm_dma_kernel<T, CFG, LA, LB, 3, 0, true>), grid, dim3(256), 0, st, la, lb, ep, rm, M, N, ktiles, per, xsplits);
+      if (deep) hipLaunchKernelGGL((igemm_dma_kernel<T, CFG, LA, LB, 4, 0, true>), k.grid, dim3(256), 0, st, la, lb, ep, rm, M, N, k.ktiles, k.per, k.xsplits);
+      else hipLaunchKernelGGL((igemm_dma_kernel<T, CFG, LA, LB, 3, 0, true>), k.grid, dim3(256), 0, st, la, lb, ep, rm, M, N, k.ktiles, k.per, k.xsplits);
       return (int)hipGetLastError();
     }
   }
-  bool deep = 4 * STAGE <= 65536 && (long)tiles * splits <= 2 * 256 && per >= 4 && stages_pref() != 3;
-  if (deep || (stages_pref() == 4 && 4 * STAGE <= 65536))
-    hipLaunchKernelGGL((igemm_dma_kernel<T, CFG, LA, LB, 4>), grid, dim3(256), 0, st, la, lb, ep, rm,
-                       M, N, ktiles, per, xsplits);
-  else if (sizeof(T) == 2 && !ep.atomic && !ep.out_f32 && !ep.preact && ep.act == CLITE_ACT_NONE && !ep.dact_aux && ep.drop_p <= 0.f && !ep.residual && !ep.bn_y &&
-           !ep.mask_after_residual)
-    // plain bf16 store (+ bias, + column statistics): the branch-free epilogue instantiation
-    hipLaunchKernelGGL((igemm_dma_kernel<T, CFG, LA, LB, 3, 2>), grid, dim3(256), 0, st, la, lb, ep, rm,
-                       M, N, ktiles, per, xsplits);
+  if ((deep && stages_pref() != 3) || (stages_pref() == 4 && 4 * STAGE <= 65536))
+    hipLaunchKernelGGL((igemm_dma_kernel<T, CFG, LA, LB, 4>), k.grid, dim3(256), 0, st, la, lb, ep, rm, M, N, k.ktiles, k.per, k.xsplits);
+  else if (sizeof(T) == 2 && ep_plain_store(ep))
+    hipLaunchKernelGGL((igemm_dma_kernel<T, CFG, LA, LB, 3, 2>), k.grid, dim3(256), 0, st, la, lb, ep, rm, M, N, k.ktiles, k.per, k.xsplits);
   else
-    hipLaunchKernelGGL((igemm_dma_kernel<T, CFG, LA, LB, 3>), grid, dim3(256), 0, st, la, lb, ep, rm,
-                       M, N, ktiles, per, xsplits);
+    hipLaunchKernelGGL((igemm_dma_kernel<T, CFG, LA, LB, 3>), k.grid, dim3(256), 0, st, la, lb, ep, rm, M, N, k.ktiles, k.per, k.xsplits);
   return (int)hipGetLastError();
+}
+
+template <typename T, class CFG, class LA, class LB>
+int launch(const LA& la, const LB& lb, const clite_epilogue& ep, int M, int N, int Ktot, int splits, hipStream_t st, RowMap rm) {
+  int rc = launch_deterministic<T, CFG>(la, lb, ep, M, N, Ktot, splits, st, rm);
+  if (rc == DECLINED) rc = launch_on_wide<T, CFG>(la, lb, ep, rm, M, N, Ktot, splits, st);
+  if (rc != DECLINED) return rc;
+  const KSplit k = ksplit<CFG>(M, N, Ktot, splits);
+  if (ep.bn_y || ep.mask_after_residual) return launch_bn_dgrad<T, CFG>(la, lb, ep, rm, M, N, k.ktiles, k.splits, st);
+  rc = launch_persistent_fwd<T, CFG>(la, lb, ep, rm, M, N, k, st);
+  return rc != DECLINED ? rc : launch_ring<T, CFG>(la, lb, ep, rm, M, N, k, st);
 }
 
 // Split-K factor for float-atomic accumulation (weight gradients). Every split adds a full output tile of atomic traffic
@@ -384,32 +462,31 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(const float* __restr
   }
 }
 
+// K splits that give a product of few (<= 48) 128 x 128 output tiles about 64 workgroups of at least two K tiles each; 0 for a product that is not one
+long fewtile_want(int M, int N, int ktiles) {
+  long tiles = (long)((M + 127) / 128) * ((N + 127) / 128);
+  if (tiles > 48 || ktiles < 8) return 0;
+  // every split adds a full f32 tile of atomic traffic (64 KB; chip-wide ~1.3 TB/s): ~64 workgroups balance that against the number of
+  // CUs fetching the weights (tools/probe_heads.py, sum over the heads' shapes: no split 482 us, 32 -> 371, 64 -> 339, 128 -> 357, 256 -> 425)
+  const int pref = splitk_ws_pref();
+  const long target = pref > 1 ? pref : 64;
+  long want = (target + tiles - 1) / tiles, cap = ktiles / 2;
+  return want > cap ? cap : want;
+}
+
 // number of K splits for the workspace form, or 0 when the launch does not qualify
 template <typename T>
 int splitk_plan(const clite_epilogue& ep, int M, int N, int ktiles) {
-  if (deterministic() || sizeof(T) != 2 || !ep.splitk_ws || ep.atomic || ep.drop_p > 0.f || ep.bn_y || ep.mask_after_residual || N % 8) return 0;
-  const int pref = splitk_ws_pref();
-  if (!pref) return 0;
-  // every split adds a full f32 tile of atomic traffic (64 KB; chip-wide ~1.3 TB/s): ~64 workgroups balance that against the number of
-  // CUs fetching the weights (tools/probe_heads.py, sum over the heads' shapes: no split 482 us, 32 -> 371, 64 -> 339, 128 -> 357, 256 -> 425)
-  const long target = pref > 1 ? pref : 64;
-  long tiles = (long)((M + 127) / 128) * ((N + 127) / 128);
-  if (tiles > 48 || ktiles < 8) return 0;
-  long want = (target + tiles - 1) / tiles, cap = ktiles / 2;
-  if (want > cap) want = cap;
+  if (deterministic() || sizeof(T) != 2 || !ep_splitk_finishable(ep) || N % 8 || !splitk_ws_pref()) return 0;
+  const long want = fewtile_want(M, N, ktiles);
   return want >= 2 ? (int)want : 0;
 }
 
 // splits of a forward-form product that accumulates into a caller-owned f32 buffer (ep.atomic on gemm_nt / gemm_nn: the loss heads' fused
 // MI blocks, loss.py): few output tiles against megabytes of weights, i.e. the workspace form's balance, not the weight gradients'
 int fewtile_splits(int M, int N, int ktiles) {
-  long tiles = (long)((M + 127) / 128) * ((N + 127) / 128);
-  if (tiles > 48 || ktiles < 8) return pick_splits(M, N, ktiles);
-  const int pref = splitk_ws_pref();
-  const long target = pref > 1 ? pref : 64;
-  long want = (target + tiles - 1) / tiles, cap = ktiles / 2;
-  if (want > cap) want = cap;
-  return want >= 1 ? (int)want : 1;
+  const long want = fewtile_want(M, N, ktiles);
+  return want ? (int)want : pick_splits(M, N, ktiles);
 }
 
 template <typename T>
@@ -424,48 +501,40 @@ clite_epilogue splitk_partial(const clite_epilogue& ep, int N) {
   return e;
 }
 
+// The forward-form products (gemm_nt, gemm_nn). run(tile, epilogue, splits) launches the caller's operands on that tile
+template <typename T, class Run>
+int gemm_fwd_form(Run run, int M, int N, int K, const clite_epilogue* ep, hipStream_t st) {
+  const int ktiles = (K + Cfg<T>::BK - 1) / Cfg<T>::BK;
+  if (int sk = splitk_plan<T>(*ep, M, N, ktiles)) {
+    int rc = run(Tile<typename Cfg<T>::C128>{}, splitk_partial(*ep, N), sk);
+    return rc ? rc : splitk_finish<T>(*ep, M, N, st);
+  }
+  const int splits = ep->atomic ? fewtile_splits(M, N, ktiles) : 1;
+  return with_cols<T>(N, [&](auto tile) { return run(tile, *ep, splits); });
+}
+
 template <typename T>
 int gemm_nt(const void* A, int lda, const void* B, int ldb, int M, int N, int K, const clite_epilogue* ep, hipStream_t st) {
   constexpr int BK = Cfg<T>::BK;
   uint32_t ab = span_bytes(M, K, lda, sizeof(T)), bb = span_bytes(N, K, ldb, sizeof(T));
-  int splits = ep->atomic ? fewtile_splits(M, N, (K + BK - 1) / BK) : 1;
-  if (int sk = splitk_plan<T>(*ep, M, N, (K + BK - 1) / BK)) {
-    clite_epilogue e1 = splitk_partial(*ep, N);
-    DmaKC<T, 128, BK, false> la{A, ab, geom_dense(M, K, lda)};
-    DmaKC<T, 128, BK, false> lb{B, bb, geom_dense(N, K, ldb)};
-    int rc = launch<T, typename Cfg<T>::C128>(la, lb, e1, M, N, K, sk, st);
-    return rc ? rc : splitk_finish<T>(*ep, M, N, st);
-  }
-  if (N <= 64) {
-    DmaKC<T, 256, BK, false> la{A, ab, geom_dense(M, K, lda)};
-    DmaKC<T, 64, BK, false> lb{B, bb, geom_dense(N, K, ldb)};
-    return launch<T, typename Cfg<T>::C256x64>(la, lb, *ep, M, N, K, splits, st);
-  }
-  DmaKC<T, 128, BK, false> la{A, ab, geom_dense(M, K, lda)};
-  DmaKC<T, 128, BK, false> lb{B, bb, geom_dense(N, K, ldb)};
-  return launch<T, typename Cfg<T>::C128>(la, lb, *ep, M, N, K, splits, st);
+  return gemm_fwd_form<T>([&](auto tile, const clite_epilogue& e, int splits) {
+    typedef decltype(tile) TL;
+    DmaKC<T, TL::ROWS, BK, false> la{A, ab, geom_dense(M, K, lda)};
+    DmaKC<T, TL::COLS, BK, false> lb{B, bb, geom_dense(N, K, ldb)};
+    return launch<T, typename TL::CFG>(la, lb, e, M, N, K, splits, st);
+  }, M, N, K, ep, st);
 }
 
 template <typename T>
 int gemm_nn(const void* A, int lda, const void* B, int ldb, int M, int N, int K, const clite_epilogue* ep, hipStream_t st) {
   constexpr int BK = Cfg<T>::BK;
   uint32_t ab = span_bytes(M, K, lda, sizeof(T)), bb = span_bytes(K, N, ldb, sizeof(T));
-  int splits = ep->atomic ? fewtile_splits(M, N, (K + BK - 1) / BK) : 1;
-  if (int sk = splitk_plan<T>(*ep, M, N, (K + BK - 1) / BK)) {
-    clite_epilogue e1 = splitk_partial(*ep, N);
-    DmaKC<T, 128, BK, false> la{A, ab, geom_dense(M, K, lda)};
-    DmaXCStrided<T, 128, BK> lb{B, bb, ldb, N, K, 1};
-    int rc = launch<T, typename Cfg<T>::C128>(la, lb, e1, M, N, K, sk, st);
-    return rc ? rc : splitk_finish<T>(*ep, M, N, st);
-  }
-  if (N <= 64) {
-    DmaKC<T, 256, BK, false> la{A, ab, geom_dense(M, K, lda)};
-    DmaXCStrided<T, 64, BK> lb{B, bb, ldb, N, K, 1};
-    return launch<T, typename Cfg<T>::C256x64>(la, lb, *ep, M, N, K, splits, st);
-  }
-  DmaKC<T, 128, BK, false> la{A, ab, geom_dense(M, K, lda)};
-  DmaXCStrided<T, 128, BK> lb{B, bb, ldb, N, K, 1};
-  return launch<T, typename Cfg<T>::C128>(la, lb, *ep, M, N, K, splits, st);
+  return gemm_fwd_form<T>([&](auto tile, const clite_epilogue& e, int splits) {
+    typedef decltype(tile) TL;
+    DmaKC<T, TL::ROWS, BK, false> la{A, ab, geom_dense(M, K, lda)};
+    DmaXCStrided<T, TL::COLS, BK> lb{B, bb, ldb, N, K, 1};
+    return launch<T, typename TL::CFG>(la, lb, e, M, N, K, splits, st);
+  }, M, N, K, ep, st);
 }
 
 template <typename T>
@@ -489,24 +558,10 @@ int check_conv(const clite_conv* c) {
   return 0;
 }
 ConvGeom geom_fwd(const clite_conv& c) {   // rows = output pixels, gather x
-  ConvGeom g;
-  g.H = c.H; g.W = c.W; g.C = c.C;
-  g.sN = c.H * c.W * c.C; g.sH = c.W * c.C; g.sW = c.C;
-  g.RH = c.Ho; g.RW = c.Wo; g.R = c.R; g.S = c.S; g.stride = c.stride; g.pad = c.pad; g.padw = c.pad;
-  g.rows = c.N * c.Ho * c.Wo; g.concat = 0;
-  g.div_hw = fastdiv_make(c.Ho * c.Wo);
-  g.div_w = fastdiv_make(c.Wo);
-  return g;
+  return geom_window(c.N, c.H, c.W, c.C, c.C, c.Ho, c.Wo, c.R, c.S, c.stride, c.pad, c.pad);
 }
 ConvGeom geom_dgrad(const clite_conv& c) {  // rows = input pixels, gather dy
-  ConvGeom g;
-  g.H = c.Ho; g.W = c.Wo; g.C = c.K;
-  g.sN = c.Ho * c.Wo * c.K; g.sH = c.Wo * c.K; g.sW = c.K;
-  g.RH = c.H; g.RW = c.W; g.R = c.R; g.S = c.S; g.stride = c.stride; g.pad = c.pad; g.padw = c.pad;
-  g.rows = c.N * c.H * c.W; g.concat = 0;
-  g.div_hw = fastdiv_make(c.H * c.W);
-  g.div_w = fastdiv_make(c.W);
-  return g;
+  return geom_window(c.N, c.Ho, c.Wo, c.K, c.K, c.H, c.W, c.R, c.S, c.stride, c.pad, c.pad);
 }
 
 template <typename T>
@@ -522,91 +577,66 @@ int conv_fwd(const void* x, const void* w, const clite_conv& c, const clite_epil
       if (rc != WIDE_NOT_TAKEN) return rc;
     }
   }
-  if (c.K <= 64) {
-    DmaKC<T, 256, BK, false> la{x, xb, geom_fwd(c)};
-    DmaKC<T, 64, BK, false> lb{w, wb, geom_dense(c.K, Ktot)};
-    return launch<T, typename Cfg<T>::C256x64>(la, lb, *ep, M, c.K, Ktot, 1, st);
-  }
-  DmaKC<T, 128, BK, false> la{x, xb, geom_fwd(c)};
-  DmaKC<T, 128, BK, false> lb{w, wb, geom_dense(c.K, Ktot)};
-  return launch<T, typename Cfg<T>::C128>(la, lb, *ep, M, c.K, Ktot, 1, st);
+  return with_cols<T>(c.K, [&](auto tile) {
+    typedef decltype(tile) TL;
+    DmaKC<T, TL::ROWS, BK, false> la{x, xb, geom_fwd(c)};
+    DmaKC<T, TL::COLS, BK, false> lb{w, wb, geom_dense(c.K, Ktot)};
+    return launch<T, typename TL::CFG>(la, lb, *ep, M, c.K, Ktot, 1, st);
+  });
 }
 
-// WT: the weight is given transposed, [C][R][S][K] — a k-contiguous (KC) operand like the forward's, instead of the k-strided XC image
+// The weight operand of a dgrad with COLS output columns (the C input channels) over taps * K: k-strided, the XC image of [K][taps][C]; or, WT, given
+// transposed as [C][taps][K] — a k-contiguous (KC) operand like the forward's
+template <typename T, int COLS, bool WT>
+auto dgrad_weight(const void* w, uint32_t wb, int C, int K, int taps) {
+  if constexpr (WT) return DmaKC<T, COLS, Cfg<T>::BK, false>{w, wb, geom_dense(C, taps * K)};
+  else return DmaXCStrided<T, COLS, Cfg<T>::BK>{w, wb, taps * C, C, K, taps};
+}
+
 template <typename T, bool WT = false>
 int conv_dgrad(const void* dy, const void* w, const clite_conv& c, const clite_epilogue* ep, hipStream_t st) {
   constexpr int BK = Cfg<T>::BK;
   int M = c.N * c.H * c.W, Ktot = c.R * c.S * c.K;
   uint32_t yb = (uint32_t)((size_t)c.N * c.Ho * c.Wo * c.K * sizeof(T)), wb = (uint32_t)((size_t)c.K * c.R * c.S * c.C * sizeof(T));
-  if constexpr (WT) {
-    if constexpr (sizeof(T) == 2) {
-      if (!deterministic() && tile_policy_value() == 0) {          // 3 x 3 / stride 1, 64 <- 64: conv_patch.hip
-        const int rc = launch_conv3x3_patch(dy, w, c, *ep, true, st);
-        if (rc != WIDE_NOT_TAKEN) return rc;
-      }
+  if constexpr (WT && sizeof(T) == 2) {
+    if (!deterministic() && tile_policy_value() == 0) {          // 3 x 3 / stride 1, 64 <- 64: conv_patch.hip
+      const int rc = launch_conv3x3_patch(dy, w, c, *ep, true, st);
+      if (rc != WIDE_NOT_TAKEN) return rc;
     }
-    if (c.R == 1 && c.S == 1 && c.pad == 0 && c.stride > 1 && ep->residual == ep->out && !ep->colsum && !ep->preact && !ep->dact_aux) {
-      int P = c.N * c.Ho * c.Wo;      // strided 1x1 shortcut: dense GEMM over the output pixels, rows scattered (see below)
-      RowMap rm;
-      rm.on = 1; rm.div_hw = fastdiv_make(c.Ho * c.Wo); rm.div_w = fastdiv_make(c.Wo); rm.H = c.H; rm.W = c.W; rm.stride = c.stride; rm.off_h = 0; rm.off_w = 0;
-      if (c.C <= 64) {
-        DmaKC<T, 256, BK, false> la{dy, yb, geom_dense(P, c.K)};
-        DmaKC<T, 64, BK, false> lb{w, wb, geom_dense(c.C, c.K)};
-        return launch<T, typename Cfg<T>::C256x64>(la, lb, *ep, P, c.C, c.K, 1, st, rm);
-      }
-      DmaKC<T, 128, BK, false> la{dy, yb, geom_dense(P, c.K)};
-      DmaKC<T, 128, BK, false> lb{w, wb, geom_dense(c.C, c.K)};
-      return launch<T, typename Cfg<T>::C128>(la, lb, *ep, P, c.C, c.K, 1, st, rm);
-    }
-    RowMap rm{};
-    if (ep->residual_subsample > 1) {
-      // clite_epilogue.residual_subsample: the compact gradient of a stride-2 shortcut as the residual of this (dense, 1 x 1 / stride 1) dgrad
-      if (ep->residual_subsample != 2 || c.R != 1 || c.S != 1 || c.stride != 1 || c.pad != 0 || (c.H & 1) || (c.W & 1) || !ep->residual || !ep->bn_y ||
-          !ep->mask_after_residual)
-        return -1;
-      rm.on = 2; rm.div_hw = fastdiv_make(c.H * c.W); rm.div_w = fastdiv_make(c.W); rm.H = c.H; rm.W = c.W; rm.stride = 2; rm.off_h = 0; rm.off_w = 0;
-    }
-    if (c.C <= 64) {
-      DmaKC<T, 256, BK, true> la{dy, yb, geom_dgrad(c)};
-      DmaKC<T, 64, BK, false> lb{w, wb, geom_dense(c.C, Ktot)};
-      return launch<T, typename Cfg<T>::C256x64>(la, lb, *ep, M, c.C, Ktot, 1, st, rm);
-    }
-    DmaKC<T, 128, BK, true> la{dy, yb, geom_dgrad(c)};
-    DmaKC<T, 128, BK, false> lb{w, wb, geom_dense(c.C, Ktot)};
-    return launch<T, typename Cfg<T>::C128>(la, lb, *ep, M, c.C, Ktot, 1, st, rm);
   }
-  if (ep->residual_subsample > 1) return -1;          // (the transposed-weight entry point only)
+  if (!WT && ep->residual_subsample > 1) return -1;          // (the transposed-weight entry point only)
   if (c.R == 1 && c.S == 1 && c.pad == 0 && c.stride > 1 && ep->residual == ep->out && !ep->colsum && !ep->preact && !ep->dact_aux) {
     // 1x1 / stride-s shortcut conv accumulated in place (dx += dgrad): only every s-th pixel of dx receives a contribution, so run
     // the dense GEMM dy[P][K] * W[K][C] over the P output pixels and scatter-add its rows (RowMap) instead of gathering a mostly
     // empty im2col over all N*H*W input pixels (s*s times the work)
     int P = c.N * c.Ho * c.Wo;
-    RowMap rm;
-    rm.on = 1; rm.div_hw = fastdiv_make(c.Ho * c.Wo); rm.div_w = fastdiv_make(c.Wo); rm.H = c.H; rm.W = c.W; rm.stride = c.stride; rm.off_h = 0; rm.off_w = 0;
-    if (c.C <= 64) {
-      DmaKC<T, 256, BK, false> la{dy, yb, geom_dense(P, c.K)};
-      DmaXCStrided<T, 64, BK> lb{w, wb, c.C, c.C, c.K, 1};
-      return launch<T, typename Cfg<T>::C256x64>(la, lb, *ep, P, c.C, c.K, 1, st, rm);
-    }
-    DmaKC<T, 128, BK, false> la{dy, yb, geom_dense(P, c.K)};
-    DmaXCStrided<T, 128, BK> lb{w, wb, c.C, c.C, c.K, 1};
-    return launch<T, typename Cfg<T>::C128>(la, lb, *ep, P, c.C, c.K, 1, st, rm);
+    const RowMap rm = row_map(1, c.Ho, c.Wo, c.H, c.W, c.stride);
+    return with_cols<T>(c.C, [&](auto tile) {
+      typedef decltype(tile) TL;
+      DmaKC<T, TL::ROWS, BK, false> la{dy, yb, geom_dense(P, c.K)};
+      return launch<T, typename TL::CFG>(la, dgrad_weight<T, TL::COLS, WT>(w, wb, c.C, c.K, 1), *ep, P, c.C, c.K, 1, st, rm);
+    });
   }
-  if (c.C <= 64) {
-    DmaKC<T, 256, BK, true> la{dy, yb, geom_dgrad(c)};
-    DmaXCStrided<T, 64, BK> lb{w, wb, c.R * c.S * c.C, c.C, c.K, c.R * c.S};
-    return launch<T, typename Cfg<T>::C256x64>(la, lb, *ep, M, c.C, Ktot, 1, st);
+  RowMap rm{};
+  if (ep->residual_subsample > 1) {
+    // clite_epilogue.residual_subsample: the compact gradient of a stride-2 shortcut as the residual of this (dense, 1 x 1 / stride 1) dgrad
+    if (ep->residual_subsample != 2 || c.R != 1 || c.S != 1 || c.stride != 1 || c.pad != 0 || (c.H & 1) || (c.W & 1) || !ep->residual || !ep->bn_y ||
+        !ep->mask_after_residual)
+      return -1;
+    rm = row_map(2, c.H, c.W, c.H, c.W, 2);
   }
-  DmaKC<T, 128, BK, true> la{dy, yb, geom_dgrad(c)};
-  DmaXCStrided<T, 128, BK> lb{w, wb, c.R * c.S * c.C, c.C, c.K, c.R * c.S};
-  return launch<T, typename Cfg<T>::C128>(la, lb, *ep, M, c.C, Ktot, 1, st);
+  return with_cols<T>(c.C, [&](auto tile) {
+    typedef decltype(tile) TL;
+    DmaKC<T, TL::ROWS, BK, true> la{dy, yb, geom_dgrad(c)};
+    return launch<T, typename TL::CFG>(la, dgrad_weight<T, TL::COLS, WT>(w, wb, c.C, c.K, c.R * c.S), *ep, M, c.C, Ktot, 1, st, rm);
+  });
 }
 
 // One parity class (ph, pw) of the dgrad of a 3x3 / stride-2 / pad-1 conv: input pixels (2*hq + ph, 2*wq + pw) only receive the
 // taps r = r0 + 2a, s = s0 + 2b with r0 = (ph + 1) & 1, s0 = (pw + 1) & 1, and ho = hq + ch - a with ch = (ph + 1 - r0) / 2: a
 // stride-1 dgrad with an na x nb window and padding (ch, cw) over the [N][H/2][W/2] sub-grid, scattered to its pixels by RowMap.
-// `wsub` holds that class's taps packed as [K][na][nb][C]. The four classes together cost 9 taps per output quad instead of the
-// 36 that a gather over all pixels and all taps (3/4 of them structurally zero) performs.
+// `wsub` holds that class's taps packed as [K][na][nb][C] (WT: [C][na][nb][K]). The four classes together cost 9 taps per output quad
+// instead of the 36 that a gather over all pixels and all taps (3/4 of them structurally zero) performs.
 template <typename T, bool WT = false>
 int conv_dgrad_s2class(const void* dy, const void* wsub, const clite_conv& c, int ph, int pw, const clite_epilogue* ep, hipStream_t st) {
   constexpr int BK = Cfg<T>::BK;
@@ -614,35 +644,15 @@ int conv_dgrad_s2class(const void* dy, const void* wsub, const clite_conv& c, in
   const int na = r0 ? 1 : 2, nb = s0 ? 1 : 2;
   const int ch = (ph + 1 - r0) / 2, cw = (pw + 1 - s0) / 2;
   const int Hq = c.H / 2, Wq = c.W / 2;
-  ConvGeom g;
-  g.H = c.Ho; g.W = c.Wo; g.C = c.K;
-  g.sN = c.Ho * c.Wo * c.K; g.sH = c.Wo * c.K; g.sW = c.K;
-  g.RH = Hq; g.RW = Wq; g.R = na; g.S = nb; g.stride = 1; g.pad = ch; g.padw = cw;
-  g.rows = c.N * Hq * Wq; g.concat = 0;
-  g.div_hw = fastdiv_make(Hq * Wq);
-  g.div_w = fastdiv_make(Wq);
-  RowMap rm;
-  rm.on = 1; rm.div_hw = g.div_hw; rm.div_w = g.div_w; rm.H = c.H; rm.W = c.W; rm.stride = 2; rm.off_h = ph; rm.off_w = pw;
+  const ConvGeom g = geom_window(c.N, c.Ho, c.Wo, c.K, c.K, Hq, Wq, na, nb, 1, ch, cw);
+  const RowMap rm = row_map(1, Hq, Wq, c.H, c.W, 2, ph, pw);
   const int M = g.rows, Ktot = na * nb * c.K;
   uint32_t yb = (uint32_t)((size_t)c.N * c.Ho * c.Wo * c.K * sizeof(T)), wb = (uint32_t)((size_t)c.K * na * nb * c.C * sizeof(T));
-  if constexpr (WT) {            // wsub = [C][na][nb][K]
-    if (c.C <= 64) {
-      DmaKC<T, 256, BK, true> la{dy, yb, g};
-      DmaKC<T, 64, BK, false> lb{wsub, wb, geom_dense(c.C, Ktot)};
-      return launch<T, typename Cfg<T>::C256x64>(la, lb, *ep, M, c.C, Ktot, 1, st, rm);
-    }
-    DmaKC<T, 128, BK, true> la{dy, yb, g};
-    DmaKC<T, 128, BK, false> lb{wsub, wb, geom_dense(c.C, Ktot)};
-    return launch<T, typename Cfg<T>::C128>(la, lb, *ep, M, c.C, Ktot, 1, st, rm);
-  }
-  if (c.C <= 64) {
-    DmaKC<T, 256, BK, true> la{dy, yb, g};
-    DmaXCStrided<T, 64, BK> lb{wsub, wb, na * nb * c.C, c.C, c.K, na * nb};
-    return launch<T, typename Cfg<T>::C256x64>(la, lb, *ep, M, c.C, Ktot, 1, st, rm);
-  }
-  DmaKC<T, 128, BK, true> la{dy, yb, g};
-  DmaXCStrided<T, 128, BK> lb{wsub, wb, na * nb * c.C, c.C, c.K, na * nb};
-  return launch<T, typename Cfg<T>::C128>(la, lb, *ep, M, c.C, Ktot, 1, st, rm);
+  return with_cols<T>(c.C, [&](auto tile) {
+    typedef decltype(tile) TL;
+    DmaKC<T, TL::ROWS, BK, true> la{dy, yb, g};
+    return launch<T, typename TL::CFG>(la, dgrad_weight<T, TL::COLS, WT>(wsub, wb, c.C, c.K, na * nb), *ep, M, c.C, Ktot, 1, st, rm);
+  });
 }
 
 template <typename T>
@@ -652,34 +662,20 @@ int conv_wgrad(const void* dy, const void* x, const clite_conv& c, float* dw, hi
   uint32_t yb = (uint32_t)((size_t)P * c.K * sizeof(T)), xb = (uint32_t)((size_t)c.N * c.H * c.W * c.C * sizeof(T));
   clite_epilogue ep = {};
   ep.out = dw; ep.ldc = Ncols; ep.out_f32 = 1; ep.atomic = 1; ep.alpha = 1.f;
-  if (c.K <= 64) {          // a 128-row tile would be half empty
-    DmaXCStrided<T, 64, BK> la{dy, yb, c.K, c.K, P, 1};
-    DmaXCGather<T, 128, BK> lb{x, xb, geom_fwd(c)};
-    return launch<T, typename Cfg<T>::C64x128>(la, lb, ep, c.K, Ncols, P, pick_splits(c.K, Ncols, (P + BK - 1) / BK, 64, 128, c.R * c.S > 1), st);
-  }
-  if (Ncols <= 64) {
-    DmaXCStrided<T, 128, BK> la{dy, yb, c.K, c.K, P, 1};
-    DmaXCGather<T, 64, BK> lb{x, xb, geom_fwd(c)};
-    return launch<T, typename Cfg<T>::C128x64>(la, lb, ep, c.K, Ncols, P, pick_splits(c.K, Ncols, (P + BK - 1) / BK, 128, 64, c.R * c.S > 1), st);
-  }
-  DmaXCStrided<T, 128, BK> la{dy, yb, c.K, c.K, P, 1};
-  DmaXCGather<T, 128, BK> lb{x, xb, geom_fwd(c)};
-  int splits = pick_splits(c.K, Ncols, (P + BK - 1) / BK, 128, 128, c.R * c.S > 1);
-  return launch<T, typename Cfg<T>::C128>(la, lb, ep, c.K, Ncols, P, splits, st);
+  auto run = [&](auto tile) {
+    typedef decltype(tile) TL;
+    DmaXCStrided<T, TL::ROWS, BK> la{dy, yb, c.K, c.K, P, 1};
+    DmaXCGather<T, TL::COLS, BK> lb{x, xb, geom_fwd(c)};
+    return launch<T, typename TL::CFG>(la, lb, ep, c.K, Ncols, P, pick_splits(c.K, Ncols, (P + BK - 1) / BK, TL::ROWS, TL::COLS, c.R * c.S > 1), st);
+  };
+  if (c.K <= 64) return run(Tile<typename Cfg<T>::C64x128>{});          // a 128-row tile would be half empty
+  if (Ncols <= 64) return run(Tile<typename Cfg<T>::C128x64>{});
+  return run(Tile<typename Cfg<T>::C128>{});
 }
 
 // 7x7/2 stem on a pre-padded NHWC4 image [N][Hp][Wp][4]: a 7x1 window over 32 "virtual" channels (8 adjacent pixels
 // x 4 channels are contiguous), K = 7*32 = 224; weights packed as [64][7][8][4] with s=7 and c=3 zero.
-ConvGeom geom_stem(int N, int Hp, int Wp, int Ho, int Wo) {
-  ConvGeom g;
-  g.H = Hp; g.W = Wp; g.C = 32;
-  g.sN = Hp * Wp * 4; g.sH = Wp * 4; g.sW = 4;
-  g.RH = Ho; g.RW = Wo; g.R = 7; g.S = 1; g.stride = 2; g.pad = 0; g.padw = 0;
-  g.rows = N * Ho * Wo; g.concat = 0;
-  g.div_hw = fastdiv_make(Ho * Wo);
-  g.div_w = fastdiv_make(Wo);
-  return g;
-}
+ConvGeom geom_stem(int N, int Hp, int Wp, int Ho, int Wo) { return geom_window(N, Hp, Wp, 32, 4, Ho, Wo, 7, 1, 2, 0, 0); }
 int check_stem(int dtype, int N, int Hp, int Wp, int Ho, int Wo) {
   if (dtype != CLITE_BF16 && dtype != CLITE_F32) return -1;
   if (N <= 0 || Wp % 2 || 2 * (Ho - 1) + 7 > Hp || 2 * (Wo - 1) + 8 > Wp) return -1;
@@ -745,34 +741,37 @@ extern "C" int clite_dbg_read(unsigned long long* host, int n) {     // diagnost
 
 extern "C" int clite_gemm_nt(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int dtype, const clite_epilogue* ep, void* stream) {
   if (check_gemm(ep, dtype, M, N, K, lda, ldb, M, N) || K % 8 || lda < K || ldb < K) return -1;
-  return dtype == CLITE_BF16 ? gemm_nt<bf16>(A, lda, B, ldb, M, N, K, ep, (hipStream_t)stream) : gemm_nt<float>(A, lda, B, ldb, M, N, K, ep, (hipStream_t)stream);
+  return with_dtype(dtype, [&](auto t) { return gemm_nt<decltype(t)>(A, lda, B, ldb, M, N, K, ep, (hipStream_t)stream); });
 }
 extern "C" int clite_gemm_nn(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int dtype, const clite_epilogue* ep, void* stream) {
   if (check_gemm(ep, dtype, M, N, K, lda, ldb, M, K) || K % 8 || lda < K || ldb < N) return -1;
-  return dtype == CLITE_BF16 ? gemm_nn<bf16>(A, lda, B, ldb, M, N, K, ep, (hipStream_t)stream) : gemm_nn<float>(A, lda, B, ldb, M, N, K, ep, (hipStream_t)stream);
+  return with_dtype(dtype, [&](auto t) { return gemm_nn<decltype(t)>(A, lda, B, ldb, M, N, K, ep, (hipStream_t)stream); });
 }
 extern "C" int clite_gemm_tn(const void* A, int lda, const void* B, int ldb, int M, int N, int K, int dtype, const clite_epilogue* ep, void* stream) {
   if (check_gemm(ep, dtype, M, N, K, lda, ldb, K, K) || M % 8 || N % 8 || lda < M || ldb < N) return -1;
-  return dtype == CLITE_BF16 ? gemm_tn<bf16>(A, lda, B, ldb, M, N, K, ep, (hipStream_t)stream) : gemm_tn<float>(A, lda, B, ldb, M, N, K, ep, (hipStream_t)stream);
+  return with_dtype(dtype, [&](auto t) { return gemm_tn<decltype(t)>(A, lda, B, ldb, M, N, K, ep, (hipStream_t)stream); });
 }
 extern "C" int clite_conv_fwd(const void* x, const void* w, const clite_conv* cv, const clite_epilogue* ep, void* stream) {
   if (check_conv(cv) || check_ep(ep, cv->K) || ep->residual_subsample > 1) return -1;
-  return cv->dtype == CLITE_BF16 ? conv_fwd<bf16>(x, w, *cv, ep, (hipStream_t)stream) : conv_fwd<float>(x, w, *cv, ep, (hipStream_t)stream);
+  return with_dtype(cv->dtype, [&](auto t) { return conv_fwd<decltype(t)>(x, w, *cv, ep, (hipStream_t)stream); });
 }
 extern "C" int clite_conv_dgrad(const void* dy, const void* w, const clite_conv* cv, const clite_epilogue* ep, void* stream) {
   if (check_conv(cv) || check_ep(ep, cv->C)) return -1;
-  return cv->dtype == CLITE_BF16 ? conv_dgrad<bf16>(dy, w, *cv, ep, (hipStream_t)stream) : conv_dgrad<float>(dy, w, *cv, ep, (hipStream_t)stream);
+  return with_dtype(cv->dtype, [&](auto t) { return conv_dgrad<decltype(t)>(dy, w, *cv, ep, (hipStream_t)stream); });
 }
-extern "C" int clite_conv_dgrad_s2class(const void* dy, const void* wsub, const clite_conv* cv, int ph, int pw, const clite_epilogue* ep, void* stream) {
+template <bool WT>
+int s2class_entry(const void* dy, const void* wsub, const clite_conv* cv, int ph, int pw, const clite_epilogue* ep, void* stream) {
   if (check_conv(cv) || check_ep(ep, cv->C)) return -1;
   if (cv->R != 3 || cv->S != 3 || cv->stride != 2 || cv->pad != 1 || (cv->H & 1) || (cv->W & 1) || (unsigned)ph > 1 || (unsigned)pw > 1) return -1;
   if (cv->C % 64 || cv->K % 64 || ep->residual_subsample > 1) return -1;
-  return cv->dtype == CLITE_BF16 ? conv_dgrad_s2class<bf16>(dy, wsub, *cv, ph, pw, ep, (hipStream_t)stream)
-                                 : conv_dgrad_s2class<float>(dy, wsub, *cv, ph, pw, ep, (hipStream_t)stream);
+  return with_dtype(cv->dtype, [&](auto t) { return conv_dgrad_s2class<decltype(t), WT>(dy, wsub, *cv, ph, pw, ep, (hipStream_t)stream); });
+}
+extern "C" int clite_conv_dgrad_s2class(const void* dy, const void* wsub, const clite_conv* cv, int ph, int pw, const clite_epilogue* ep, void* stream) {
+  return s2class_entry<false>(dy, wsub, cv, ph, pw, ep, stream);
 }
 extern "C" int clite_conv_dgrad_wt(const void* dy, const void* wt, const clite_conv* cv, const clite_epilogue* ep, void* stream) {
   if (check_conv(cv) || check_ep(ep, cv->C)) return -1;
-  return cv->dtype == CLITE_BF16 ? conv_dgrad<bf16, true>(dy, wt, *cv, ep, (hipStream_t)stream) : conv_dgrad<float, true>(dy, wt, *cv, ep, (hipStream_t)stream);
+  return with_dtype(cv->dtype, [&](auto t) { return conv_dgrad<decltype(t), true>(dy, wt, *cv, ep, (hipStream_t)stream); });
 }
 // The block-output BatchNorm backward folded into the 1 x 1 convolution's input gradient (include/clite.h, ABI v12): A = [dz | y] as a two-slot "window" over
 // the pair buffer [2][M][K] — the dgrad gather with R = 2, S = 1, pad 1 over a 2 x M "image" whose single output row is the M pixels: r = 0 reads slot 1 (y),
@@ -783,37 +782,26 @@ extern "C" int clite_conv_dgrad_bnfold(const void* pair, const void* w2, int M, 
   if (!pair || !w2 || M <= 0 || K <= 0 || Cin <= 0 || K % 64 || Cin % 8 || check_ep(ep, Cin)) return -1;
   if (!ep->bn_y || !ep->relu_bits || !ep->bias || ep->residual || ep->mask_after_residual || ep->out_f32 || ep->alpha != 1.f || ep->residual_subsample > 1) return -1;
   if (!fits32((size_t)2 * M * K, sizeof(T)) || (size_t)2 * M * K >= ((size_t)1 << 31)) return -1;
-  ConvGeom g;
-  g.H = 2; g.W = M; g.C = K;
-  g.sN = 0; g.sH = M * K; g.sW = K;
-  g.RH = 1; g.RW = M; g.R = 2; g.S = 1; g.stride = 1; g.pad = 1; g.padw = 0;
-  g.rows = M; g.concat = 1;
-  g.div_hw = fastdiv_make(M);
-  g.div_w = fastdiv_make(M);
+  ConvGeom g = geom_window(1, 2, M, K, K, 1, M, 2, 1, 1, 1, 0);
+  g.sN = 0; g.concat = 1;
   const uint32_t ab = (uint32_t)((size_t)2 * M * K * sizeof(T)), wb = (uint32_t)((size_t)Cin * 2 * K * sizeof(T));
   hipStream_t st = (hipStream_t)stream;
   // K = 256, Cin = 64 (the 56 x 56 stage): the streaming kernel of fold_dgrad.hip
   const int rc = launch_fold_dgrad_rows(pair, w2, M, K, Cin, *ep, st);
   if (rc != WIDE_NOT_TAKEN) return rc;
-  if (Cin <= 64) {
-    DmaKC<T, 256, BK, true> la{pair, ab, g};
-    DmaKC<T, 64, BK, false> lb{w2, wb, geom_dense(Cin, 2 * K)};
-    return launch<T, typename Cfg<T>::C256x64>(la, lb, *ep, M, Cin, 2 * K, 1, st);
-  }
-  DmaKC<T, 128, BK, true> la{pair, ab, g};
-  DmaKC<T, 128, BK, false> lb{w2, wb, geom_dense(Cin, 2 * K)};
-  return launch<T, typename Cfg<T>::C128>(la, lb, *ep, M, Cin, 2 * K, 1, st);
+  return with_cols<T>(Cin, [&](auto tile) {
+    typedef decltype(tile) TL;
+    DmaKC<T, TL::ROWS, BK, true> la{pair, ab, g};
+    DmaKC<T, TL::COLS, BK, false> lb{w2, wb, geom_dense(Cin, 2 * K)};
+    return launch<T, typename TL::CFG>(la, lb, *ep, M, Cin, 2 * K, 1, st);
+  });
 }
 extern "C" int clite_conv_dgrad_s2class_wt(const void* dy, const void* wtsub, const clite_conv* cv, int ph, int pw, const clite_epilogue* ep, void* stream) {
-  if (check_conv(cv) || check_ep(ep, cv->C)) return -1;
-  if (cv->R != 3 || cv->S != 3 || cv->stride != 2 || cv->pad != 1 || (cv->H & 1) || (cv->W & 1) || (unsigned)ph > 1 || (unsigned)pw > 1) return -1;
-  if (cv->C % 64 || cv->K % 64 || ep->residual_subsample > 1) return -1;
-  return cv->dtype == CLITE_BF16 ? conv_dgrad_s2class<bf16, true>(dy, wtsub, *cv, ph, pw, ep, (hipStream_t)stream)
-                                 : conv_dgrad_s2class<float, true>(dy, wtsub, *cv, ph, pw, ep, (hipStream_t)stream);
+  return s2class_entry<true>(dy, wtsub, cv, ph, pw, ep, stream);
 }
 extern "C" int clite_conv_wgrad(const void* dy, const void* x, const clite_conv* cv, float* dw, void* stream) {
   if (check_conv(cv) || !dw) return -1;
-  return cv->dtype == CLITE_BF16 ? conv_wgrad<bf16>(dy, x, *cv, dw, (hipStream_t)stream) : conv_wgrad<float>(dy, x, *cv, dw, (hipStream_t)stream);
+  return with_dtype(cv->dtype, [&](auto t) { return conv_wgrad<decltype(t)>(dy, x, *cv, dw, (hipStream_t)stream); });
 }
 
 // The 64 -> 64 3 x 3 / stride 1 weight gradient on the patch-resident kernel (conv_patch.hip). Returns 1 when the problem is not one it covers
@@ -842,13 +830,11 @@ extern "C" int clite_stem_wgrad_patch(const void* dy, const void* xpad, int dtyp
 
 extern "C" int clite_stem_fwd(const void* xpad, const void* wv, int dtype, int N, int Hp, int Wp, int Ho, int Wo, const clite_epilogue* ep, void* stream) {
   if (check_stem(dtype, N, Hp, Wp, Ho, Wo) || check_ep(ep, 64)) return -1;
-  return dtype == CLITE_BF16 ? stem_fwd<bf16>(xpad, wv, N, Hp, Wp, Ho, Wo, ep, (hipStream_t)stream)
-                             : stem_fwd<float>(xpad, wv, N, Hp, Wp, Ho, Wo, ep, (hipStream_t)stream);
+  return with_dtype(dtype, [&](auto t) { return stem_fwd<decltype(t)>(xpad, wv, N, Hp, Wp, Ho, Wo, ep, (hipStream_t)stream); });
 }
 extern "C" int clite_stem_wgrad(const void* dy, const void* xpad, int dtype, int N, int Hp, int Wp, int Ho, int Wo, float* dwv, void* stream) {
   if (check_stem(dtype, N, Hp, Wp, Ho, Wo) || !dwv) return -1;
-  return dtype == CLITE_BF16 ? stem_wgrad<bf16>(dy, xpad, N, Hp, Wp, Ho, Wo, dwv, (hipStream_t)stream)
-                             : stem_wgrad<float>(dy, xpad, N, Hp, Wp, Ho, Wo, dwv, (hipStream_t)stream);
+  return with_dtype(dtype, [&](auto t) { return stem_wgrad<decltype(t)>(dy, xpad, N, Hp, Wp, Ho, Wo, dwv, (hipStream_t)stream); });
 }
 extern "C" int clite_stem_pack(const float* w, void* wv, int dtype, void* stream) {
   if (!w || !wv) return -1;

@@ -46,6 +46,34 @@ def lib():
     return _lib
 
 
+def launch_log(clear=True):
+    """The simulator's launch log as [(kernel instantiation, (grid x, y, z), block x)], oldest first; cleared afterwards unless told not to."""
+    L = lib()
+    L.wavesim_log_get.restype = C.c_char_p
+    dims = (C.c_uint * 4)()
+    out = []
+    for i in range(L.wavesim_log_size()):
+        name = L.wavesim_log_get(i, dims)
+        out.append((name.decode(), (dims[0], dims[1], dims[2]), dims[3]))
+    if clear:
+        L.wavesim_log_clear()
+    return out
+
+
+def clear_launch_log():
+    lib().wavesim_log_clear()
+
+
+def set_dry_run(on):
+    """Dry run: a launch is recorded in the log and returns without executing the kernel body."""
+    lib().wavesim_set_dry_run(int(bool(on)))
+
+
+def launched(family):
+    """Names in the launch log (which is left as it is) that belong to the kernel family `family`, e.g. 'igemm_dma_bn_kernel'."""
+    return [n for n, _, _ in launch_log(clear=False) if "::" + family + "<" in n or n.startswith(family + "<")]
+
+
 def to_bf16(x):
     """float32 ndarray -> uint16 bf16 bits, round-to-nearest-even."""
     x = np.ascontiguousarray(x, dtype=np.float32)

@@ -5,7 +5,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from simlib import Conv, bf16_round, from_bf16, lib, make_ep, pack_relu_bits, ptr, to_bf16
+from simlib import Conv, bf16_round, clear_launch_log, from_bf16, launch_log, lib, make_ep, pack_relu_bits, ptr, to_bf16
 
 BF16, F32 = 0, 1
 
@@ -36,6 +36,11 @@ def _prep(x, dtype):
 
 def outbuf_like(dtype, shape):
     return np.zeros(shape, np.uint16 if dtype == BF16 else np.float32)
+
+
+def kernels_launched():
+    """the kernel instantiations launched since the last call (or clear_launch_log()), in order: what a test named after a kernel form checks it ran"""
+    return [name for name, _, _ in launch_log()]
 
 
 def _close(got, ref, rel=2e-3):
@@ -91,6 +96,7 @@ def test_gemm_splitk_workspace_form(kind, M, N, K):
     if kind == "nt":
         ep = make_ep(out, ldc, bias=bias, act=1, preact=pre, residual=Rb, colsum=colsum, alpha=0.5)
         ep.splitk_ws = ptr(ws)
+        clear_launch_log()
         assert lib().clite_gemm_nt(ptr(Ab), K, ptr(Bb), K, M, N, K, BF16, C.byref(ep), None) == 0
         zz = 0.5 * z + bias
         ref = np.maximum(zz, 0) + R[:, :N]
@@ -99,9 +105,12 @@ def test_gemm_splitk_workspace_form(kind, M, N, K):
         aux, auxb = _prep(rng.standard_normal((M, 2 * N), dtype=np.float32), BF16)
         ep = make_ep(out, ldc, dact_aux=auxb, dact=1, residual=Rb, colsum=colsum)
         ep.splitk_ws = ptr(ws)
+        clear_launch_log()
         assert lib().clite_gemm_nn(ptr(Ab), K, ptr(Bb), N, M, N, K, BF16, C.byref(ep), None) == 0
         ref = z * (aux[:, :N] > 0) + R[:, :N]
     assert np.abs(ws).max() > 0                   # the split-K form ran (the fused path never touches the workspace)
+    partial, finish = kernels_launched()          # ... as the 4-wave engine on 128 x 128 tiles, then the finishing kernel
+    assert "::igemm_dma_kernel<__bf16, clite::TileCfg<128, 128, " in partial and "::splitk_finish_kernel<__bf16>" in finish
     got = from_bf16(out)
     _close(got[:, :N], ref, 6e-3)
     assert not got[:, N:].any()
@@ -265,7 +274,10 @@ def test_conv_fwd_1x1_row_range_persistent_form(N, H, W, Cc, K, st):
     csr = np.zeros((4, 3, K), np.float32)
     ep = make_ep(y, K, colsum=csr)
     ep.colsum_replicas, ep.colsum_stride = 4, 3 * K
+    clear_launch_log()
     assert lib().clite_conv_fwd(ptr(xb), ptr(wb), C.byref(cv), C.byref(ep), None) == 0
+    (kernel,) = kernels_launched()          # FORM 4 of the row-range kernel
+    assert "::igemm_dma_bn_kernel<__bf16, " in kernel and ", 4, false, false, false>(" in kernel
     ref = conv_ref(x, w, st, 0)
     got = from_bf16(y)
     assert np.abs(got - ref).max() <= 6e-3 * np.abs(ref).max()
@@ -344,7 +356,10 @@ def test_stem_weight_gradient_patch_resident(N, H, W, extra_rows):
     dw = np.full((64, 7, 7, 3), 0.5, np.float32)
     L = lib()
     L.clite_stem_wgrad_patch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    clear_launch_log()
     assert L.clite_stem_wgrad_patch(ptr(dyb), ptr(xpad), BF16, N, Hp, Wp, Ho, Wo, ptr(dw), ptr(ws), nb.value, None) == 0
+    patch, reduce = kernels_launched()
+    assert "::stem_wgrad_patch_kernel<" in patch and "::stem_wgrad_reduce_kernel" in reduce
     ref = conv_wgrad_ref(dy, imgr.transpose(0, 2, 3, 1), (64, 7, 7, 3), 2, 3)
     _close(dw - 0.5, ref, 2e-3)
     dwv = np.zeros((64, 7, 8, 4), np.float32)
@@ -355,7 +370,9 @@ def test_stem_weight_gradient_patch_resident(N, H, W, extra_rows):
     assert L.clite_stem_wgrad_patch(ptr(dyb), ptr(xpad), BF16, N, Hp, Wp, Ho, Wo, ptr(dw), ptr(ws), 1024, None) == 1
     assert L.clite_stem_wgrad_patch(ptr(dyb), ptr(xpad), F32, N, Hp, Wp, Ho, Wo, ptr(dw), ptr(ws), nb.value, None) == 1
     Wo2 = Wo - 4          # a width that is not a multiple of 16
+    clear_launch_log()
     assert L.clite_stem_wgrad_patch(ptr(dyb), ptr(xpad), BF16, N, Hp, Wp, Ho, Wo2, ptr(dw), ptr(ws), nb.value, None) == 1
+    assert kernels_launched() == []
 
 
 
@@ -565,7 +582,10 @@ def test_folded_dgrad_streaming_kernel_k256_c64(M):
         ep = make_ep(out, Cin, bias=bias, colsum=d2, relu_bits=bits)
         ep.colsum_replicas, ep.colsum_stride = R, 3 * Cin
         ep.bn_y, ep.bn_stats, ep.bn_replicas, ep.bn_rstride, ep.bn_inv_count = ptr(y2b), ptr(st2), R, 3 * Cin, 1.0 / M
+        clear_launch_log()
         assert L.clite_conv_dgrad_bnfold(ptr(pair), ptr(w2), M, K, Cin, C.byref(ep), None) == 0
+        (kernel,) = kernels_launched()
+        assert ("::fold_dgrad_rows_kernel" in kernel) if policy == 0 else ("::igemm_dma_bn_kernel<__bf16, " in kernel and ", 5, false, false, false>(" in kernel)
         return from_bf16(out), d2.sum(0)
     got, d = run(0)                    # the streaming kernel
     ref = (y @ w2f[:, 0, :].T + dz @ w2f[:, 1, :].T + bias) * mask
@@ -710,10 +730,17 @@ def test_bert_epilogue_forms_compiled_in(M, N, K, tile_policy):
     bias = rng.standard_normal(N).astype(np.float32)
     z = A @ B.T
     cdf = lambda x: 0.5 * (1 + erf(x / np.sqrt(2)))
+    wide_tile = {1: "WideCfg<128, 128, ", 2: "WideCfg<256, 128, ", 3: "WideCfg<256, 256, "}[tile_policy]
+
+    def ran_wide_form(form):          # the last launch: the 8-wave kernel on the forced tile with WideEpiForm `form` compiled in
+        (kernel,) = kernels_launched()
+        return "::igemm_wide_kernel<clite::" + wide_tile in kernel and kernel.split(">(")[0].endswith(", %d" % form)
+    clear_launch_log()
     # form 3
     out, pre = np.zeros((M, N), np.uint16), np.zeros((M, N), np.uint16)
     ep = make_ep(out, N, bias=bias, act=2, preact=pre)
     assert lib().clite_gemm_nt(ptr(Ab), K, ptr(Bb), K, M, N, K, BF16, C.byref(ep), None) == 0
+    assert ran_wide_form(3)
     _close(from_bf16(pre), z + bias, 6e-3)
     _close(from_bf16(out), (z + bias) * cdf(z + bias), 6e-3)
     # form 4, with and without the column sums; the floats behind the sums (what colsum_rows = 1 must not touch) stay as they were
@@ -724,6 +751,7 @@ def test_bert_epilogue_forms_compiled_in(M, N, K, tile_policy):
         ep = make_ep(out, N, dact_aux=auxb, dact=2, colsum=colsum if with_sums else None)
         ep.colsum_rows = 1
         assert lib().clite_gemm_nt(ptr(Ab), K, ptr(Bb), K, M, N, K, BF16, C.byref(ep), None) == 0
+        assert ran_wide_form(4)
         gp = cdf(aux) + aux * np.exp(-0.5 * aux * aux) / np.sqrt(2 * np.pi)
         _close(from_bf16(out), z * gp, 6e-3)
         if with_sums:
@@ -733,6 +761,7 @@ def test_bert_epilogue_forms_compiled_in(M, N, K, tile_policy):
     out = np.zeros((M, N), np.uint16)
     ep = make_ep(out, N, residual=Rb)
     assert lib().clite_gemm_nt(ptr(Ab), K, ptr(Bb), K, M, N, K, BF16, C.byref(ep), None) == 0
+    assert ran_wide_form(6)
     _close(from_bf16(out), z + R, 6e-3)
     # form 5 against the run-time-flag epilogue of the 4-wave kernel
     res = []
@@ -741,6 +770,11 @@ def test_bert_epilogue_forms_compiled_in(M, N, K, tile_policy):
         out = np.zeros((M, N), np.uint16)
         ep = make_ep(out, N, bias=bias, drop_p=0.25, drop_seed=1234, drop_site=5, residual=Rb)
         assert lib().clite_gemm_nt(ptr(Ab), K, ptr(Bb), K, M, N, K, BF16, C.byref(ep), None) == 0
+        if pol == 4:
+            (kernel,) = kernels_launched()
+            assert "::igemm_dma_kernel" in kernel          # (the two-K-group or the ring kernel: the 4-wave engine's run-time-flag epilogue)
+        else:
+            assert ran_wide_form(5)
         res.append(from_bf16(out))
     assert lib().clite_set_tile_policy(tile_policy) == 0
     dropped = np.isclose(res[1], R, atol=0)                # a dropped element is the bare residual
@@ -772,7 +806,10 @@ def test_patch_resident_conv3x3_64ch(N, H, W):
     csr = np.zeros((4, 3, K), np.float32)
     ep = make_ep(y, K, colsum=csr)
     ep.colsum_replicas, ep.colsum_stride = 4, 3 * K
+    clear_launch_log()
     assert lib().clite_conv_fwd(ptr(xb), ptr(wb), C.byref(cv), C.byref(ep), None) == 0
+    (kernel,) = kernels_launched()
+    assert "::conv3x3_patch_kernel<0>" in kernel
     ref = conv_ref(x, w, 1, 1).reshape(M, K)
     got = from_bf16(y)
     _close(got, ref, 6e-3)
@@ -785,6 +822,8 @@ def test_patch_resident_conv3x3_64ch(N, H, W):
     y4 = np.zeros((M, K), np.uint16)
     ep4 = make_ep(y4, K)
     assert lib().clite_conv_fwd(ptr(xb), ptr(wb), C.byref(cv), C.byref(ep4), None) == 0
+    (kernel,) = kernels_launched()
+    assert "::igemm_dma_kernel" in kernel
     assert lib().clite_set_tile_policy(0) == 0
     _close(got, from_bf16(y4), 8e-3)
     # input gradient on the transposed weights, plain store
@@ -792,6 +831,8 @@ def test_patch_resident_conv3x3_64ch(N, H, W):
     g = conv_dgrad_ref(dy, w, (N, H, W, Cc), 1, 1).reshape(M, Cc)
     dx = np.zeros((M, Cc), np.uint16)
     assert lib().clite_conv_dgrad_wt(ptr(dyb), ptr(wtb), C.byref(cv), C.byref(make_ep(dx, Cc)), None) == 0
+    (kernel,) = kernels_launched()
+    assert "::conv3x3_patch_kernel<0>" in kernel
     _close(from_bf16(dx), g, 6e-3)
     # BatchNorm-backward form (igemm.h FORM 1): v = acc where the bit is set, sum v and sum v (bn_y - mean)
     aux = rng.standard_normal((M, Cc)).astype(np.float32)
@@ -805,6 +846,8 @@ def test_patch_resident_conv3x3_64ch(N, H, W):
     ep.colsum_replicas, ep.colsum_stride = 2, 3 * Cc
     ep.bn_y, ep.bn_stats, ep.bn_replicas, ep.bn_rstride, ep.bn_inv_count = ptr(ybb), ptr(fstats), 2, 3 * Cc, 1.0 / M
     assert lib().clite_conv_dgrad_wt(ptr(dyb), ptr(wtb), C.byref(cv), C.byref(ep), None) == 0
+    (kernel,) = kernels_launched()
+    assert "::conv3x3_patch_kernel<1>" in kernel
     gv = from_bf16(out)
     _close(gv, g * (aux > 0), 6e-3)
     assert ((gv == 0) | (aux > 0)).all()
@@ -832,15 +875,20 @@ def test_patch_resident_wgrad3x3_64ch(N, H, W):
     ws = np.full(nb.value // 4, np.nan, np.float32)          # scratch arrives dirty
     dw = np.full((K, 3, 3, Cc), 0.5, np.float32)
     lib().clite_conv_wgrad_patch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]
+    clear_launch_log()
     assert lib().clite_conv_wgrad_patch(ptr(dyb), ptr(xb), C.byref(cv), ptr(dw), ptr(ws), nb.value, None) == 0
+    patch, reduce = kernels_launched()
+    assert "::conv3x3_wgrad_patch_kernel" in patch and "::wgrad_patch_reduce_kernel" in reduce
     ref = conv_wgrad_ref(dy, x, (K, 3, 3, Cc), 1, 1)
     _close(dw - 0.5, ref, 2e-3)
     dw2 = np.zeros((K, 3, 3, Cc), np.float32)
     assert lib().clite_conv_wgrad(ptr(dyb), ptr(xb), C.byref(cv), ptr(dw2), None) == 0
     _close(dw - 0.5, dw2, 2e-3)
+    clear_launch_log()
     assert lib().clite_conv_wgrad_patch(ptr(dyb), ptr(xb), C.byref(cv), ptr(dw), ptr(ws), nb.value - 4, None) == 1
     cv2 = Conv(BF16, N, H, W, Cc, K, 3, 3, 2, 1, (H - 1) // 2 + 1, (W - 1) // 2 + 1)
     assert lib().clite_conv_wgrad_patch(ptr(dyb), ptr(xb), C.byref(cv2), ptr(dw), ptr(ws), nb.value, None) == 1
+    assert kernels_launched() == []
 
 
 @pytest.mark.policy_independent
@@ -896,6 +944,7 @@ def test_f32_split_bf16_form():
     rng = np.random.default_rng(11)
     try:
         assert L.clite_set_f32_split(1) == 0 and L.clite_get_f32_split() == 1
+        clear_launch_log()
         M, N, K = 200, 136, 104
         A = rng.standard_normal((M, K)).astype(np.float32)
         B = rng.standard_normal((N, K)).astype(np.float32)
@@ -940,9 +989,14 @@ def test_f32_split_bf16_form():
         assert L.clite_conv_wgrad(ptr(dy), ptr(x), C.byref(cv), ptr(dw), None) == 0
         rw = conv_wgrad_ref(dy.astype(np.float64), x.astype(np.float64), (Kc, 3, 3, Cc), 1, 1)
         assert np.abs(dw - rw).max() / np.abs(rw).max() < 3e-5
+        split = kernels_launched()          # all six launches on the split-bf16 instantiations (SPLIT = true) of the f32 kernels
+        assert len(split) == 6 and all(("::igemm_dma_kernel<float, " in k and ", true>(" in k) or "::igemm_dma_bn_kernel<float, " in k for k in split)
+        assert [k for k in split if "::igemm_dma_bn_kernel<" in k] == [split[4]] and ", 0, true, false, false>(" in split[4]
     finally:
         L.clite_set_f32_split(0)
     # the default (exact) form on the first problem, for scale
     out_e = np.zeros((M, N), np.float32)
     assert L.clite_gemm_nt(ptr(A), K, ptr(B), K, M, N, K, F32, C.byref(make_ep(out_e, N, out_f32=True)), None) == 0
+    (kernel,) = kernels_launched()
+    assert "::igemm_dma_kernel<float, " in kernel and ", false>(" in kernel
     assert np.abs(out_e - ref).max() / np.abs(ref).max() < 2e-6

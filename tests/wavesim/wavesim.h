@@ -25,6 +25,7 @@
 #include <functional>
 #include <memory>
 #include <thread>
+#include <typeinfo>
 #include <vector>
 
 #define __global__
@@ -77,8 +78,16 @@ extern thread_local dim3 gridDim;
 inline void __syncthreads() { wavesim::g_block->bar->arrive_and_wait(); }
 inline void wave_barrier_() { wavesim::g_block->waves[wavesim::g_wave].bar->arrive_and_wait(); }
 
-template <class K, class... Args>
-void wavesim_launch(K kernel, dim3 grid, dim3 block, Args... args) {
+// Launch log (wavesim.cpp): every launch appends (resolved kernel instantiation, grid, block); in dry run that is all a launch does, so the
+// tests can pin which kernel the host launchers select for a shape of any size (tests/test_wavesim_dispatch.py).
+namespace wavesim {
+template <auto K> struct KernelTag {};        // typeid(KernelTag<K>) demangles to the instantiation's full name, template arguments included
+bool record_launch(const std::type_info& tag, dim3 grid, dim3 block);      // true: dry run, do not execute
+}  // namespace wavesim
+
+template <auto kernel, class... Args>
+void wavesim_launch(dim3 grid, dim3 block, Args... args) {
+  if (wavesim::record_launch(typeid(wavesim::KernelTag<kernel>), grid, block)) return;
   unsigned nthreads = block.x * block.y * block.z;
   assert(block.y == 1 && block.z == 1 && "wavesim: 1-D blocks only");
   assert(nthreads % 64 == 0 && "wavesim: block size must be a multiple of 64");
@@ -107,7 +116,7 @@ void wavesim_launch(K kernel, dim3 grid, dim3 block, Args... args) {
       }
 }
 #define hipLaunchKernelGGL(kernel, grid, block, shmem, stream, ...) \
-  wavesim_launch(kernel, dim3(grid), dim3(block), ##__VA_ARGS__)
+  wavesim_launch<(kernel)>(dim3(grid), dim3(block), ##__VA_ARGS__)
 
 // ---------------------------------------------------------------- types
 typedef __bf16 bf16;
