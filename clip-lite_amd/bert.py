@@ -2,7 +2,7 @@
 encoder.py:165-170 builds with BertConfig(num_hidden_layers=n)) and the hand-scheduled forward/backward executor.
 
 Per layer: one fused QKV GEMM ([3*768] outputs; q/k/v weights are adjacent in the parameter arena), per-head attention
-kernel (L <= 32), output projection with bias + dropout + residual in the GEMM epilogue, LayerNorm, FFN with the GELU
+kernel (L <= 128; MPNet 32), output projection with bias + dropout + residual in the GEMM epilogue, LayerNorm, FFN with the GELU
 (and its saved pre-activation) in the epilogue, second LayerNorm. Dropout masks are regenerated from (seed, site, index).
 """
 import torch
@@ -153,14 +153,24 @@ def _linear_grads(rt, lin, dy, x, M, dw=None, db=None, bias_done=False, defer=No
         hip.colsum(rt.dt, dy, db, M, N)
 
 
+MAX_TOKENS = 128      # the attention kernels' cap (csrc/bert_ops.hip: four key tiles of 32); MPNet and the fp8 forward stay at 32
+
+
 def bert_forward(rt, net, input_ids, attention_mask, step):
-    """input_ids/attention_mask: int64 [B][L] on the device, L <= 32. Returns (pooler_output [B][H], ctx).
+    """input_ids/attention_mask: int64 [B][L] on the device, L <= 128 for BERT (MAX_TOKENS; 33 and up run the four-key-tile attention kernels) and
+    L <= 32 for MPNet and for the fp8 forward. Returns (pooler_output [B][H], ctx).
     net: BertModel, or mpnet.MPNetModel — the same executor with MPNet's four differences (mpnet.py): embeddings without token types and with
     position ids counted from the ids, a relative-position bias (built here once per step from the trained table) in every layer's attention,
     and the masked mean over the last layer's tokens as the output instead of the pooler."""
     B, L = input_ids.shape
-    if L > 32:
-        raise RuntimeError("clip_lite_amd: the attention kernel supports captions of at most 32 tokens (reference config.py:69: 30)")
+    if L > MAX_TOKENS:
+        raise RuntimeError(f"clip_lite_amd: the attention kernels support captions of at most {MAX_TOKENS} tokens (got {L}; reference config.py:69: 30)")
+    if L > 32 and net.kind == "mpnet":
+        raise RuntimeError(f"clip_lite_amd: the MPNet text encoder supports captions of at most 32 tokens (got {L}): its relative-position bias "
+                           "tile and bucket table are 32-token objects; only the BERT text encoder runs up to 128")
+    if L > 32 and rt.fp8_text and rt.lowp:
+        raise RuntimeError(f"clip_lite_amd: the fp8 forward (--fp8) is measured for captions of at most 32 tokens only (got {L}); run longer "
+                           "captions without it")
     dt, A = rt.dt, rt.arena
     Hd, heads, inner = net.hidden, net.heads, net.inner
     M = B * L

@@ -806,6 +806,364 @@ __global__ __launch_bounds__(1024) void attention_bias_grad_reduce_kernel(const 
   }
 }
 
+// ------------------------------------------------------------------------------------------------ attention, 32 < L <= 128
+// The same definition as the 32-token kernels above on up to four key tiles of 32: one workgroup per (batch, head), two-pass softmax over the whole
+// score row (no running maximum), probabilities recomputed in backward, no atomics and a fixed summation order. The dropout multiplier of p[i][j]
+// is drawn from element index ((bh*128 + i)*128 + j), four consecutive j per Philox call, in both families and both directions. Rows >= L of a
+// sample belong to the next sample (or lie past the buffer): every global access is guarded by row < L.
+constexpr int AL_L = 128;
+
+DEV float al_dropmult(const Drop& drop, int bh, int i, int j) {
+  if (!(drop.p > 0.f)) return 1.f;
+  float u[4];
+  rng_uniform4(drop.seed, drop.site, ((size_t)bh * AL_L + i) * AL_L + (j & ~3), u);
+  const int e = j & 3;
+  const float ue = e == 0 ? u[0] : (e == 1 ? u[1] : (e == 2 ? u[2] : u[3]));
+  return ue >= drop.p ? 1.0f / (1.0f - drop.p) : 0.f;
+}
+DEV float al_madd(const int64_t* mask, int b, int L, int j) {
+  return (j < L) ? ((mask && mask[(size_t)b * L + j] == 0) ? AT_NEG : 0.f) : -INFINITY;
+}
+
+// ---- exact f32 on the VALU: four waves, wave w takes the query rows (forward, dQ) and then the key rows (dK, dV) w, w + 4, ...; the lanes of a
+// wave hold the 128 entries of that score row / column two apiece (j = lane, lane + 64) and hand them to the 64 head columns through LDS
+struct AlSmem {
+  float q[AL_L * AT_PQ], k[AL_L * AT_PQ], v[AL_L * AT_PQ];
+  float madd[AL_L];
+  float row[4][2][AL_L];      // [wave][iteration parity]: one barrier per iteration is enough
+};
+struct AlBwdSmem {
+  float q[AL_L * AT_PQ], k[AL_L * AT_PQ], v[AL_L * AT_PQ], dO[AL_L * AT_PQ];
+  float madd[AL_L], mx[AL_L], den[AL_L], t[AL_L];      // per query row: softmax maximum and denominator, sum_j dP*P
+  float vec[4][2][2][AL_L];                            // [wave][iteration parity][dS | dropped P]
+};
+
+template <typename T>
+DEV void al_load_rows(const T* base, size_t row_stride, int L, float* dst, int tid) {
+  for (int idx = tid; idx < AL_L * 8; idx += 256) {
+    int r = idx >> 3, c = (idx & 7) * 8;
+    float v[8];
+    if (r < L) load8(base + (size_t)r * row_stride + c, v); else zero8(v);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) dst[r * AT_PQ + c + e] = v[e];
+  }
+}
+DEV float al_dot(const float* a, const float* b) {
+  float s = 0.f;
+#pragma unroll 16
+  for (int d = 0; d < AT_D; ++d) s += a[d] * b[d];
+  return s;
+}
+template <typename T> DEV void al_store(T* p, float v) {
+  if constexpr (sizeof(T) == 2) *p = f2bf(v); else *p = v;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void attention_long_fwd_kernel(const T* qkv, const int64_t* mask, T* ctx, int B, int L, int H, Drop drop) {
+  seed_resolve(drop.seed, drop.site);
+  __shared__ AlSmem sm;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int bh = blockIdx.x, b = bh / H, h = bh % H;
+  const size_t ld = (size_t)3 * H * AT_D;
+  const T* base = qkv + (size_t)b * L * ld + h * AT_D;
+  al_load_rows(base, ld, L, sm.q, tid);
+  al_load_rows(base + H * AT_D, ld, L, sm.k, tid);
+  al_load_rows(base + 2 * H * AT_D, ld, L, sm.v, tid);
+  if (tid < AL_L) sm.madd[tid] = al_madd(mask, b, L, tid);
+  __syncthreads();
+  for (int it = 0; it < (L + 3) / 4; ++it) {
+    const int i = it * 4 + wave;
+    float* row = sm.row[wave][it & 1];
+    if (i < L) {
+      const float s0 = al_dot(sm.q + i * AT_PQ, sm.k + lane * AT_PQ) * 0.125f + sm.madd[lane];
+      const float s1 = al_dot(sm.q + i * AT_PQ, sm.k + (lane + 64) * AT_PQ) * 0.125f + sm.madd[lane + 64];
+      const float mx = wave_max(fmaxf(s0, s1));
+      const float e0 = __expf(s0 - mx), e1 = __expf(s1 - mx);      // keys >= L: exp(-inf) = 0
+      const float den = wave_sum(e0 + e1);
+      row[lane] = e0 / den * al_dropmult(drop, bh, i, lane);
+      row[lane + 64] = e1 / den * al_dropmult(drop, bh, i, lane + 64);
+    }
+    __syncthreads();
+    if (i < L) {
+      float o = 0.f;
+      for (int j = 0; j < L; ++j) o += row[j] * sm.v[j * AT_PQ + lane];
+      al_store(ctx + ((size_t)b * L + i) * ((size_t)H * AT_D) + h * AT_D + lane, o);
+    }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void attention_long_bwd_kernel(const T* qkv, const int64_t* mask, const T* dctx, T* dqkv, int B, int L, int H, Drop drop) {
+  seed_resolve(drop.seed, drop.site);
+  __shared__ AlBwdSmem sm;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int bh = blockIdx.x, b = bh / H, h = bh % H;
+  const size_t ld = (size_t)3 * H * AT_D;
+  const T* base = qkv + (size_t)b * L * ld + h * AT_D;
+  al_load_rows(base, ld, L, sm.q, tid);
+  al_load_rows(base + H * AT_D, ld, L, sm.k, tid);
+  al_load_rows(base + 2 * H * AT_D, ld, L, sm.v, tid);
+  al_load_rows(dctx + (size_t)b * L * ((size_t)H * AT_D) + h * AT_D, (size_t)H * AT_D, L, sm.dO, tid);
+  if (tid < AL_L) sm.madd[tid] = al_madd(mask, b, L, tid);
+  __syncthreads();
+  T* obase = dqkv + (size_t)b * L * ld + h * AT_D;
+  const int iters = (L + 3) / 4;
+  // query rows: P, dP = m * dO V^T, dS = P * (dP - sum_j dP*P) for one row i; dQ[i] = dS[i] K / 8. The row's softmax statistics stay in LDS.
+  for (int it = 0; it < iters; ++it) {
+    const int i = it * 4 + wave;
+    float* ds = sm.vec[wave][it & 1][0];
+    if (i < L) {
+      const float s0 = al_dot(sm.q + i * AT_PQ, sm.k + lane * AT_PQ) * 0.125f + sm.madd[lane];
+      const float s1 = al_dot(sm.q + i * AT_PQ, sm.k + (lane + 64) * AT_PQ) * 0.125f + sm.madd[lane + 64];
+      const float mx = wave_max(fmaxf(s0, s1));
+      const float e0 = __expf(s0 - mx), e1 = __expf(s1 - mx);
+      const float den = wave_sum(e0 + e1);
+      const float p0 = e0 / den, p1 = e1 / den;
+      const float dp0 = al_dot(sm.dO + i * AT_PQ, sm.v + lane * AT_PQ) * al_dropmult(drop, bh, i, lane);
+      const float dp1 = al_dot(sm.dO + i * AT_PQ, sm.v + (lane + 64) * AT_PQ) * al_dropmult(drop, bh, i, lane + 64);
+      const float t = wave_sum(dp0 * p0 + dp1 * p1);
+      ds[lane] = p0 * (dp0 - t);
+      ds[lane + 64] = p1 * (dp1 - t);
+      if (lane == 0) { sm.mx[i] = mx; sm.den[i] = den; sm.t[i] = t; }
+    }
+    __syncthreads();
+    if (i < L) {
+      float dq = 0.f;
+      for (int j = 0; j < L; ++j) dq += ds[j] * sm.k[j * AT_PQ + lane];
+      al_store(obase + (size_t)i * ld + lane, dq * 0.125f);
+    }
+  }
+  __syncthreads();
+  // key rows: column j of dS and of the dropped P from the saved statistics (lane = query i, i + 64); dK[j] = dS[:, j]^T Q / 8, dV[j] = Pd[:, j]^T dO,
+  // summed over the queries in ascending order
+  for (int it = 0; it < iters; ++it) {
+    const int j = it * 4 + wave;
+    float* ds = sm.vec[wave][it & 1][0];
+    float* pd = sm.vec[wave][it & 1][1];
+    if (j < L) {
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        const int i = lane + 64 * half;
+        float dsv = 0.f, pdv = 0.f;
+        if (i < L) {
+          const float s = al_dot(sm.q + i * AT_PQ, sm.k + j * AT_PQ) * 0.125f + sm.madd[j];
+          const float p = __expf(s - sm.mx[i]) / sm.den[i];
+          const float mul = al_dropmult(drop, bh, i, j);
+          const float dp = al_dot(sm.dO + i * AT_PQ, sm.v + j * AT_PQ) * mul;
+          dsv = p * (dp - sm.t[i]);
+          pdv = p * mul;
+        }
+        ds[i] = dsv;
+        pd[i] = pdv;
+      }
+    }
+    __syncthreads();
+    if (j < L) {
+      float dk = 0.f, dv = 0.f;
+      for (int i = 0; i < L; ++i) {
+        dk += ds[i] * sm.q[i * AT_PQ + lane];
+        dv += pd[i] * sm.dO[i * AT_PQ + lane];
+      }
+      al_store(obase + (size_t)j * ld + H * AT_D + lane, dk * 0.125f);
+      al_store(obase + (size_t)j * ld + 2 * H * AT_D + lane, dv);
+    }
+  }
+}
+
+// ---- bf16 on v_mfma_f32_32x32x16_bf16: NT = ceil(L / 32) key tiles (2..4), one workgroup of NT waves per (batch, head), wave w owning query tile w.
+// Forward is the S^T = K Q^T / O^T = V^T P^T scheme of attention_mfma_fwd_kernel looped over the key tiles: a query's whole score row sits in NT
+// accumulators of its lane pair, so the softmax is the same two passes. Backward keeps the key on the lane (S = Q K^T, dP = dO V^T) for the wave's
+// query tile against all key tiles, leaves dS^T and the dropped P^T in LDS as bf16 images ([key][query]), and after one barrier wave w forms dK, dV
+// of key tile w (B operand: 8 consecutive queries of one key row; summed over the query tiles in ascending order) and dQ of query tile w (B operand:
+// the transposing read of the dS^T image).
+template <int NT> struct AlmFwdSmem { char v[32 * NT * AM_PI]; float madd[32 * NT]; };
+template <int NT> struct AlmBwdSmem {
+  static constexpr int PT = 64 * NT + 16;      // [32 NT][32 NT] bf16 image pitch
+  char q[32 * NT * AM_PI], k[32 * NT * AM_PI], d[32 * NT * AM_PI], ts[32 * NT * PT], tp[32 * NT * PT];
+  unsigned char keep[32 * NT][8 * NT];         // keep bits of p[i][4 c .. 4 c + 3]: one Philox call each
+  float madd[32 * NT];
+};
+template <int NT> DEV void alm_load_image(const bf16* base, size_t ld, int L, char* img, int tid) {
+  for (int c = tid; c < 32 * NT * 8; c += 64 * NT) {
+    int r = c >> 3, ch = c & 7;
+    u32x4 v = {0u, 0u, 0u, 0u};
+    if (r < L) v = *(const u32x4*)(base + (size_t)r * ld + ch * 8);
+    *(u32x4*)(img + r * AM_PI + ch * 16) = v;
+  }
+}
+
+template <int NT>
+__global__ __launch_bounds__(64 * NT) void attention_long_mfma_fwd_kernel(const bf16* qkv, const int64_t* mask, bf16* ctx, int B, int L, int H, Drop drop) {
+  seed_resolve(drop.seed, drop.site);
+  __shared__ __attribute__((aligned(16))) AlmFwdSmem<NT> S;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int bh = blockIdx.x, b = bh / H, h = bh % H;
+  const size_t ld = (size_t)3 * H * 64, ldc = (size_t)H * 64;
+  const bf16* qb = qkv + (size_t)b * L * ld + h * 64;
+  alm_load_image<NT>(qb + 2 * H * 64, ld, L, S.v, tid);
+  if (tid < 32 * NT) S.madd[tid] = al_madd(mask, b, L, tid);
+  const int Lq = L - 32 * wave;      // rows of this wave's query tile inside the sample (> 0: L > 32 (NT - 1))
+  bf16x8 qf[4];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) qf[ks] = am_frag_rows(qb + (size_t)32 * wave * ld, ld, Lq, ks, lane);
+  f32x16 acc[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {      // S^T[j][i] = sum_d K[j][d] Q[i][d], key tile t
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) acc[t] = mfma32_bf16(am_frag_rows(qb + H * 64 + (size_t)32 * t * ld, ld, L - 32 * t, ks, lane), qf[ks], acc[t]);
+  }
+  __syncthreads();
+  // softmax over j (NT accumulators x the two lane halves) for the query i = 32 wave + (lane & 31)
+  float mx = -INFINITY;
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      acc[t][r] = acc[t][r] * 0.125f + S.madd[32 * t + am_row(r, lane)];
+      mx = fmaxf(mx, acc[t][r]);
+    }
+  mx = fmaxf(mx, wave_shfl_xor(mx, 32));
+  float den = 0.f;
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc[t][r] = __expf(acc[t][r] - mx); den += acc[t][r]; }
+  den += wave_shfl_xor(den, 32);
+  const float inv = 1.0f / den;
+  const int i = 32 * wave + (lane & 31);
+  const float ksc = drop.p > 0.f ? 1.0f / (1.0f - drop.p) : 1.f;
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      float u[4] = {1.f, 1.f, 1.f, 1.f};
+      if (drop.p > 0.f) rng_uniform4(drop.seed, drop.site, ((size_t)bh * AL_L + i) * AL_L + 32 * t + 8 * g + 4 * (lane >> 5), u);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) acc[t][4 * g + e] *= inv * (u[e] >= drop.p ? ksc : 0.f);
+    }
+  // O^T[d][i] = sum_j V^T[d][j] P^T[j][i], key tiles in ascending order
+#pragma unroll
+  for (int db = 0; db < 2; ++db) {
+    f32x16 o;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[r] = 0.f;
+#pragma unroll
+    for (int t = 0; t < NT; ++t)
+#pragma unroll
+      for (int s = 0; s < 2; ++s) o = mfma32_bf16(am_frag_tr_acc<AM_PI>(S.v + 32 * t * AM_PI, db * 32, s, lane), am_acc_frag(acc[t], s), o);
+    am_store_T(ctx + ((size_t)b * L + 32 * wave) * ldc + h * 64, ldc, Lq, db * 32, o, 1.f, lane);
+  }
+}
+
+template <int NT>
+__global__ __launch_bounds__(64 * NT) void attention_long_mfma_bwd_kernel(const bf16* qkv, const int64_t* mask, const bf16* dctx, bf16* dqkv, int B, int L, int H,
+                                                                           Drop drop) {
+  seed_resolve(drop.seed, drop.site);
+  constexpr int PT = AlmBwdSmem<NT>::PT;
+  __shared__ __attribute__((aligned(16))) AlmBwdSmem<NT> S;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int bh = blockIdx.x, b = bh / H, h = bh % H;
+  const size_t ld = (size_t)3 * H * 64, ldc = (size_t)H * 64;
+  const bf16* qb = qkv + (size_t)b * L * ld + h * 64;
+  const bf16* dob = dctx + (size_t)b * L * ldc + h * 64;
+  alm_load_image<NT>(qb, ld, L, S.q, tid);
+  alm_load_image<NT>(qb + H * 64, ld, L, S.k, tid);
+  alm_load_image<NT>(dob, ldc, L, S.d, tid);
+  if (tid < 32 * NT) S.madd[tid] = al_madd(mask, b, L, tid);
+  for (int c = lane; c < 32 * 8 * NT; c += 64) {      // keep bits of this wave's 32 query rows
+    const int i = 32 * wave + c / (8 * NT), jq = c % (8 * NT);
+    float u[4] = {1.f, 1.f, 1.f, 1.f};
+    if (drop.p > 0.f) rng_uniform4(drop.seed, drop.site, ((size_t)bh * AL_L + i) * AL_L + 4 * jq, u);
+    unsigned bits = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) bits |= (u[e] >= drop.p ? 1u : 0u) << e;
+    S.keep[i][jq] = (unsigned char)bits;
+  }
+  const int Lq = L - 32 * wave;
+  bf16x8 qf[4], dof[4];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    qf[ks] = am_frag_rows(qb + (size_t)32 * wave * ld, ld, Lq, ks, lane);
+    dof[ks] = am_frag_rows(dob + (size_t)32 * wave * ldc, ldc, Lq, ks, lane);
+  }
+  f32x16 p[NT], dp[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { p[t][r] = 0.f; dp[t][r] = 0.f; }
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      p[t] = mfma32_bf16(qf[ks], am_frag_rows(qb + H * 64 + (size_t)32 * t * ld, ld, L - 32 * t, ks, lane), p[t]);            // S[i][j]
+      dp[t] = mfma32_bf16(dof[ks], am_frag_rows(qb + 2 * H * 64 + (size_t)32 * t * ld, ld, L - 32 * t, ks, lane), dp[t]);     // dP[i][j] = dO V^T
+    }
+  }
+  __syncthreads();
+  const int jl = lane & 31;
+  const float ksc = drop.p > 0.f ? 1.0f / (1.0f - drop.p) : 1.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {      // softmax over j = across the 32 lanes of a half and the NT tiles, per register row i
+    const int il = am_row(r, lane);
+    float e[NT], mx = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) { e[t] = p[t][r] * 0.125f + S.madd[32 * t + jl]; mx = fmaxf(mx, e[t]); }
+#pragma unroll
+    for (int m = 16; m >= 1; m >>= 1) mx = fmaxf(mx, wave_shfl_xor(mx, m));
+    float den = 0.f;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) { e[t] = __expf(e[t] - mx); den += e[t]; }
+#pragma unroll
+    for (int m = 16; m >= 1; m >>= 1) den += wave_shfl_xor(den, m);
+    float tt = 0.f;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      e[t] = (il < Lq) ? e[t] / den : 0.f;
+      const float mul = ((S.keep[32 * wave + il][8 * t + (jl >> 2)] >> (jl & 3)) & 1) ? ksc : 0.f;
+      dp[t][r] *= mul;
+      tt += dp[t][r] * e[t];
+      p[t][r] = e[t] * mul;      // dropped P
+    }
+#pragma unroll
+    for (int m = 16; m >= 1; m >>= 1) tt += wave_shfl_xor(tt, m);
+#pragma unroll
+    for (int t = 0; t < NT; ++t) dp[t][r] = e[t] * (dp[t][r] - tt);      // dS
+  }
+  // the images: ts[j][i] = dS[i][j], tp[j][i] = Pd[i][j] for this wave's 32 queries (4 consecutive i per register group)
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+      union { bf16 e[4]; u32x2 u; } ks, kp;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { ks.e[e] = f2bf(dp[t][4 * g + e]); kp.e[e] = f2bf(p[t][4 * g + e]); }
+      const int off = (32 * t + jl) * PT + (32 * wave + 8 * g + 4 * (lane >> 5)) * 2;
+      *(u32x2*)(S.ts + off) = ks.u;
+      *(u32x2*)(S.tp + off) = kp.u;
+    }
+  __syncthreads();
+  bf16* ob = dqkv + ((size_t)b * L + 32 * wave) * ld + h * 64;      // key tile `wave` for dK, dV; query tile `wave` for dQ
+#pragma unroll
+  for (int db = 0; db < 2; ++db) {
+    f32x16 dv, dk, dq;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { dv[r] = 0.f; dk[r] = 0.f; dq[r] = 0.f; }
+#pragma unroll
+    for (int s = 0; s < 2 * NT; ++s) {
+      Chunk16 bp, bs;
+      const int off = (32 * wave + jl) * PT + (16 * s + 8 * (lane >> 5)) * 2;
+      bp.u = *(const u32x4*)(S.tp + off);
+      bs.u = *(const u32x4*)(S.ts + off);
+      dv = mfma32_bf16(am_frag_tr<AM_PI>(S.d, db * 32, s, lane), bp.h, dv);      // dV^T[d][j] = sum_i dO^T[d][i] Pd[i][j]
+      dk = mfma32_bf16(am_frag_tr<AM_PI>(S.q, db * 32, s, lane), bs.h, dk);      // dK^T[d][j] = sum_i Q^T[d][i] dS[i][j]
+      dq = mfma32_bf16(am_frag_tr<AM_PI>(S.k, db * 32, s, lane), am_frag_tr<PT>(S.ts, 32 * wave, s, lane), dq);   // dQ^T[d][i] = sum_j K^T[d][j] dS^T[j][i]
+    }
+    am_store_T(ob + 2 * H * 64, ld, Lq, db * 32, dv, 1.f, lane);
+    am_store_T(ob + H * 64, ld, Lq, db * 32, dk, 0.125f, lane);
+    am_store_T(ob, ld, Lq, db * 32, dq, 0.125f, lane);
+  }
+}
+
 // BertPooler backward through tanh: out = dy * (1 - y^2)
 template <typename T>
 __global__ __launch_bounds__(256) void tanh_bwd_kernel(const T* dy, const T* y, T* out, size_t n8) {
@@ -916,9 +1274,17 @@ extern "C" int clite_embed_bwd(int dtype, const int64_t* ids, const void* d, flo
 
 extern "C" int clite_attention_fwd(int dtype, const void* qkv, const int64_t* mask, void* ctx, int B, int L, int H,
                                    float drop_p, uint64_t drop_seed, uint32_t drop_site, void* stream) {
-  if (B <= 0 || L <= 0 || L > AT_L || H <= 0 || !qkv || !ctx) return -1;
+  if (B <= 0 || L <= 0 || L > AL_L || H <= 0 || !qkv || !ctx) return -1;
   Drop d{drop_p, drop_seed, drop_site};
   hipStream_t st = (hipStream_t)stream;
+  if (L > AT_L) {      // 33..128: one workgroup per (batch, head), a wave per 32-query tile
+#define AL_FWD(NT) hipLaunchKernelGGL(attention_long_mfma_fwd_kernel<NT>, dim3(B * H), dim3(64 * NT), 0, st, (const bf16*)qkv, mask, (bf16*)ctx, B, L, H, d)
+    DISPATCH(dtype,
+             if (L <= 64) AL_FWD(2); else if (L <= 96) AL_FWD(3); else AL_FWD(4),
+             hipLaunchKernelGGL(attention_long_fwd_kernel<float>, dim3(B * H), dim3(256), 0, st, (const float*)qkv, mask, (float*)ctx, B, L, H, d));
+#undef AL_FWD
+    return (int)hipGetLastError();
+  }
   DISPATCH(dtype,
            hipLaunchKernelGGL(attention_mfma_fwd_kernel<false>, dim3((B * H + 3) / 4), dim3(256), 0, st, (const bf16*)qkv, mask, (bf16*)ctx, B, L, H, d, AttnBias<false>{}),
            hipLaunchKernelGGL(attention_fwd_kernel<float>, dim3(B * H), dim3(64), 0, st, (const float*)qkv, mask, (float*)ctx, B, L, H, d, AttnBias<false>{}));
@@ -927,9 +1293,17 @@ extern "C" int clite_attention_fwd(int dtype, const void* qkv, const int64_t* ma
 
 extern "C" int clite_attention_bwd(int dtype, const void* qkv, const int64_t* mask, const void* dctx, void* dqkv, int B, int L, int H,
                                    float drop_p, uint64_t drop_seed, uint32_t drop_site, void* stream) {
-  if (B <= 0 || L <= 0 || L > AT_L || H <= 0 || !qkv || !dctx || !dqkv) return -1;
+  if (B <= 0 || L <= 0 || L > AL_L || H <= 0 || !qkv || !dctx || !dqkv) return -1;
   Drop d{drop_p, drop_seed, drop_site};
   hipStream_t st = (hipStream_t)stream;
+  if (L > AT_L) {
+#define AL_BWD(NT) hipLaunchKernelGGL(attention_long_mfma_bwd_kernel<NT>, dim3(B * H), dim3(64 * NT), 0, st, (const bf16*)qkv, mask, (const bf16*)dctx, (bf16*)dqkv, B, L, H, d)
+    DISPATCH(dtype,
+             if (L <= 64) AL_BWD(2); else if (L <= 96) AL_BWD(3); else AL_BWD(4),
+             hipLaunchKernelGGL(attention_long_bwd_kernel<float>, dim3(B * H), dim3(256), 0, st, (const float*)qkv, mask, (const float*)dctx, (float*)dqkv, B, L, H, d));
+#undef AL_BWD
+    return (int)hipGetLastError();
+  }
   DISPATCH(dtype,
            hipLaunchKernelGGL(attention_mfma_bwd_kernel<false>, dim3((B * H + 1) / 2), dim3(128), 0, st, (const bf16*)qkv, mask, (const bf16*)dctx, (bf16*)dqkv, B, L, H, d, AttnBias<false>{}),
            hipLaunchKernelGGL(attention_bwd_kernel<float>, dim3(B * H), dim3(64), 0, st, (const float*)qkv, mask, (const float*)dctx, (float*)dqkv, B, L, H, d, AttnBias<false>{}));

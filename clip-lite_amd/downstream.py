@@ -158,7 +158,7 @@ def build_zero_shot_parser():
     parser.add_argument("--data-root", required=True, help="Image folder root/val/<class>/<image>, or 'random' for the synthetic source.")
     parser.add_argument("--prompt", default="a picture of a {}.", help="Prompt template; {} is replaced by the class name (reference "
                                                                       "zero_shot.py:74-85).")
-    parser.add_argument("--max-length", type=int, default=30, help="Prompt token length (padded).")
+    parser.add_argument("--max-length", type=int, default=30, help="Prompt token length (padded); at most 128 with the BERT tower, 32 with MPNet.")
     parser.add_argument("--batch-size", type=int, default=128)
     parser.add_argument("--cpu-workers", type=int, default=2)
     parser.add_argument("--num-gpus-per-machine", type=int, default=1, help="Only 1 is supported.")
@@ -420,7 +420,7 @@ def build_cluster_parser():
 def embed_captions(model, captions, max_length, vocab="", batch_size=256, text_model="bert-base-uncased"):
     """f32 [N][768] on the model's device: the text encoder's features (eval mode, no projection head) of every caption through
     clite_l2_normalize. Stands in for the reference's paraphrase-mpnet-base-v2 sentence encoder (scripts/cluster.py:115-124), which does not
-    exist offline."""
+    exist offline. max_length (DATA.MAX_CAPTION_LENGTH): up to 128 tokens with the BERT tower, 32 with MPNet (bert.bert_forward)."""
     from . import hip
     rt, enc = model.runtime, model.text_encoder
     device = next(model.parameters()).device

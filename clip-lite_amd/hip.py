@@ -824,10 +824,13 @@ def embed_bwd(dt, ids, d, dword, dpos, M, L, Cc, vocab, padding_idx=-1):
 
 
 def attention_fwd(dt, qkv, mask, ctx, B, L, H, drop=NO_DROP):
+    """ctx [B*L][H*64] = dropout(softmax(q k^T / 8 + mask)) v of qkv [B*L][3*H*64] for L <= 128: the one-tile kernels up to 32 tokens, the
+    four-key-tile kernels (one workgroup per (batch, head)) for 33..128; a longer L is an error (-1 from the library)."""
     check(lib().clite_attention_fwd(dt, p(qkv), p(mask), p(ctx), B, L, H, drop[0], drop[1], drop[2], stream_ptr(qkv)), "attention_fwd")
 
 
 def attention_bwd(dt, qkv, mask, dctx, dqkv, B, L, H, drop=NO_DROP):
+    """dqkv of attention_fwd for L <= 128, the probabilities and the dropout mask recomputed from qkv and the same `drop`; no atomics."""
     check(lib().clite_attention_bwd(dt, p(qkv), p(mask), p(dctx), p(dqkv), B, L, H, drop[0], drop[1], drop[2], stream_ptr(qkv)), "attention_bwd")
 
 

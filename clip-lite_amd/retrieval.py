@@ -36,7 +36,7 @@ def embed_images(model, images: torch.Tensor, batch_size: int = 128) -> torch.Te
 
 @torch.no_grad()
 def embed_texts(model, input_ids: torch.Tensor, attention_mask: torch.Tensor, batch_size: int = 128) -> torch.Tensor:
-    """input_ids / attention_mask: int64 [N][L <= 32] -> L2-normalised projected embeddings [N][2048].
+    """input_ids / attention_mask: int64 [N][L <= 128] (BERT; 32 for MPNet) -> L2-normalised projected embeddings [N][2048].
     Reference retrieval.py:90-108: text_projector(text_encoder({...})) then F.normalize."""
     rt = model.runtime
     enc, proj = model.text_encoder, model.loss.global_d.text_block

@@ -739,8 +739,10 @@ def main(_A: argparse.Namespace):
     if dist.is_master_process():
         checkpoint_manager = CheckpointManager(_A.checkpoints_dir + _C.RUN_ID, model=model, optimizer=optimizer, scheduler=scheduler, scaler=scaler)
 
+    # the caption length the step is captured at: the attention kernels' cap, 128 tokens for the BERT tower and 32 for MPNet (bert.bert_forward)
+    text_kind = getattr(getattr(getattr(model, "text_encoder", None), "strans", None), "kind", "bert")
     step = TrainStep(model, optimizer, scheduler, scaler, _C.OPTIM.CLIP_GRAD_NORM, exchange, graph=not _A.no_hip_graph,
-                     pad_to=min(int(_C.DATA.MAX_CAPTION_LENGTH), 32), allow_eager_fallback=_A.allow_eager_fallback, defer_update=True)
+                     pad_to=min(int(_C.DATA.MAX_CAPTION_LENGTH), 128 if text_kind == "bert" else 32), allow_eager_fallback=_A.allow_eager_fallback, defer_update=True)
     for iteration in range(start_iteration + 1, _C.OPTIM.NUM_ITERATIONS + 1):
         if clusters and iteration == _C.DATA.NEGATIVE_SAMPLING_START_ITERATION and loader_type == "normal":      # reference train.py:190-203
             logger.info("Starting clustered negative sampling, loading new dataloaders...")

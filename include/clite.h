@@ -452,8 +452,11 @@ int clite_embed_fwd(int dtype, const int64_t* ids, const void* word, const void*
  * behind reference encoder.py:163-170); -1 = none. */
 int clite_embed_bwd(int dtype, const int64_t* ids, const void* d, float* dword, float* dpos, int M, int L, int C, int vocab, int padding_idx,
                     void* stream);
-/* BertSelfAttention core for L <= 32, head size 64: qkv [B*L][3*H*64] (q|k|v), mask int64 [B][L] (1 = attend) or NULL,
- * ctx [B*L][H*64] = dropout(softmax(q k^T / 8 + (1-mask)*finfo.min)) v */
+/* BertSelfAttention core for L <= 128, head size 64: qkv [B*L][3*H*64] (q|k|v), mask int64 [B][L] (1 = attend) or NULL,
+ * ctx [B*L][H*64] = dropout(softmax(q k^T / 8 + (1-mask)*finfo.min)) v. L <= 32: one wave per (batch, head) on one 32 x 32 score tile;
+ * 33 <= L <= 128: one workgroup per (batch, head), a wave per 32-query tile over up to four key tiles (whole score row in registers, two-pass
+ * softmax, no atomics: bit-exact reruns). L > 128 returns -1. The dropout multiplier of p[i][j] comes from element index ((bh*32 + i)*32 + j)
+ * for L <= 32 and ((bh*128 + i)*128 + j) above; backward recomputes the probabilities and the mask from qkv and the same (seed, site). */
 int clite_attention_fwd(int dtype, const void* qkv, const int64_t* mask, void* ctx, int B, int L, int H,
                         float drop_p, uint64_t drop_seed, uint32_t drop_site, void* stream);
 int clite_attention_bwd(int dtype, const void* qkv, const int64_t* mask, const void* dctx, void* dqkv, int B, int L, int H,

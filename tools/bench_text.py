@@ -1,5 +1,7 @@
 """Text-tower timing: forward + backward of the BERT and of the MPNet tower in the same process (B = 128, L = 30, 12 layers, bf16), and the attention
 kernels alone with and without the relative-position bias. Prints one JSON line. The yardstick is the BERT tower of the same commit.
+With --length above 32 (up to 128) only the BERT side runs (MPNet stays at 32 tokens), and the attention section adds the kernels with dropout off
+beside torch.nn.functional.scaled_dot_product_attention forward + backward at the same shape and mask in the same process.
 
     python tools/bench_text.py [--batch 128] [--length 30] [--layers 12] [--repeats 20]
 """
@@ -98,6 +100,8 @@ def attention(B, L, H, repeats):
                 fn()
         return timeit(many, repeats) / INNER
 
+    if L > 32:
+        return attention_long(B, L, H, per_launch, qkv, dctx, ctx, dqkv, drop)
     return {
         "fwd": per_launch(lambda: hip.attention_fwd(hip.BF16, qkv, mask, ctx, B, L, H, drop)),
         "fwd_bias": per_launch(lambda: hip.attention_bias_fwd(hip.BF16, qkv, mask, bias, ctx, B, L, H, drop)),
@@ -105,6 +109,33 @@ def attention(B, L, H, repeats):
         "bwd_bias": per_launch(lambda: hip.attention_bias_bwd(hip.BF16, qkv, mask, bias, table, dctx, dqkv, partials, B, L, H, drop)),
         "bias_build": per_launch(lambda: hip.attention_bias_build(rel, table, bias, H, L)),
         "bias_grad_reduce_12_layers": per_launch(lambda: hip.attention_bias_grad_reduce(partials12, drel, 12 * B, H)),
+    }
+
+
+def attention_long(B, L, H, per_launch, qkv, dctx, ctx, dqkv, drop):
+    """33..128 tokens: the kernels with dropout on (as trained) and off, and torch's fused attention with the same ragged mask, dropout off"""
+    import torch.nn.functional as F
+    from clip_lite_amd import hip
+    mask = torch.ones(B, L, dtype=torch.long, device="cuda")
+    mask[::3, L - 5:] = 0
+    x = qkv.view(B, L, 3, H, 64)
+    q, k, v = (x[:, :, i].permute(0, 2, 1, 3).contiguous().requires_grad_(True) for i in range(3))      # [B][H][L][64], as SDPA wants them
+    amask = (mask != 0)[:, None, None, :].expand(B, 1, L, L)
+    dO = dctx.view(B, L, H, 64).permute(0, 2, 1, 3).contiguous()
+
+    def sdpa():
+        o = F.scaled_dot_product_attention(q, k, v, attn_mask=amask)
+        torch.autograd.grad(o, (q, k, v), dO)
+
+    def ours(d):
+        hip.attention_fwd(hip.BF16, qkv, mask, ctx, B, L, H, d)
+        hip.attention_bwd(hip.BF16, qkv, mask, dctx, dqkv, B, L, H, d)
+
+    return {
+        "fwd": per_launch(lambda: hip.attention_fwd(hip.BF16, qkv, mask, ctx, B, L, H, drop)),
+        "bwd": per_launch(lambda: hip.attention_bwd(hip.BF16, qkv, mask, dctx, dqkv, B, L, H, drop)),
+        "fwd_bwd_no_dropout": per_launch(lambda: ours(hip.NO_DROP)),
+        "torch_sdpa_fwd_bwd_no_dropout": per_launch(sdpa),
     }
 
 
@@ -118,8 +149,10 @@ def main():
     out = {"device": torch.cuda.get_device_name(0), "batch": a.batch, "length": a.length, "layers": a.layers, "dtype": "bf16", "unit": "us (median)"}
     out["attention_kernels"] = attention(a.batch, a.length, 12, a.repeats)
     print(json.dumps(out["attention_kernels"]), file=sys.stderr, flush=True)
-    out["tower_fwd_bwd"] = {"bert": tower("bert-base-uncased", a.layers, a.batch, a.length, a.repeats), "mpnet": tower(MPNET, a.layers, a.batch, a.length, a.repeats)}
-    out["tower_fwd_bwd"]["mpnet_over_bert"] = out["tower_fwd_bwd"]["mpnet"] / out["tower_fwd_bwd"]["bert"]
+    out["tower_fwd_bwd"] = {"bert": tower("bert-base-uncased", a.layers, a.batch, a.length, a.repeats)}
+    if a.length <= 32:
+        out["tower_fwd_bwd"]["mpnet"] = tower(MPNET, a.layers, a.batch, a.length, a.repeats)
+        out["tower_fwd_bwd"]["mpnet_over_bert"] = out["tower_fwd_bwd"]["mpnet"] / out["tower_fwd_bwd"]["bert"]
     print(json.dumps(out))
 
 
