@@ -1,7 +1,7 @@
 """Command lines of the downstream evaluations: `linear_clf.py` (linear probe / fine-tune, reference linear_clf.py:25-300) and `zero_shot.py`
-(reference zero_shot.py), on ImageClassifier / zero_shot_counts (classify.py); `voc_clf.py` (svm.py) and `retrieval.py` (retrieval.py). One
-GPU: the reference's multi-GPU launch, hipGraph capture of the classification step, and the `clip` / `imagenet` initialisations (the `clip`
-package, torchvision downloads) are not available."""
+(reference zero_shot.py), on ImageClassifier / zero_shot_counts (classify.py); `voc_clf.py` (svm.py), `knn_clf.py` (knn.py) and `retrieval.py`
+(retrieval.py). One GPU: the reference's multi-GPU launch, hipGraph capture of the classification step, and the `clip` / `imagenet`
+initialisations (the `clip` package, torchvision downloads) are not available."""
 import argparse
 import os
 
@@ -254,20 +254,25 @@ def checkpoint_path(checkpoint_dir: str, iteration: int) -> str:
     return os.path.join(checkpoint_dir, f"checkpoint_{iteration}.pth")
 
 
-def run_checkpoint_loop(checkpoint_dir, start_iter, freq, evaluate, load):
+def _report_map(test_map):
+    """voc_clf.py's line and file entry for one evaluation: the mAP, a fraction, as a percentage."""
+    print("Test mAP: " + str(test_map * 100))
+    return test_map * 100
+
+
+def run_checkpoint_loop(checkpoint_dir, start_iter, freq, evaluate, load, filename="voc07_mAP.txt", report=_report_map):
     """Reference voc_clf.py:218-237: evaluate (-> mAP as a fraction), print it, merge {iteration: mAP x 100} into <checkpoint_dir>/voc07_mAP.txt
-    (JSON), then load checkpoint_<iteration + freq>.pth and go on until that load fails ("Completed!"). Returns the merged results."""
+    (JSON), then load checkpoint_<iteration + freq>.pth and go on until that load fails ("Completed!"). Returns the merged results. Another
+    evaluation (knn_clf.py) names its own file and its own `report`, which prints evaluate()'s result and returns the JSON entry of the iteration."""
     import json
-    out = os.path.join(checkpoint_dir, "voc07_mAP.txt")
+    out = os.path.join(checkpoint_dir, filename)
     results = {}
     if os.path.exists(out):
         with open(out) as f:
             results = json.load(f)
     it = int(start_iter)
     while True:
-        test_map = evaluate()
-        print("Test mAP: " + str(test_map * 100))
-        results[str(it)] = test_map * 100
+        results[str(it)] = report(evaluate())
         with open(out, "w") as f:
             json.dump(results, f)
         it += int(freq)
@@ -334,6 +339,91 @@ def voc_clf_main(_A):
 
 def voc_clf_cli(argv=None):
     return voc_clf_main(build_voc_clf_parser().parse_args(argv))
+
+
+# ------------------------------------------------------------------------------------------------ weighted k-NN
+def build_knn_parser():
+    parser = common_parser(description="Weighted k-nearest-neighbour classification on the frozen features of a pretrained model.")
+    parser.set_defaults(num_gpus_per_machine=1)
+    group = parser.add_argument_group("Downstream config arguments.")
+    group.add_argument("--down-config", metavar="FILE", help="Path to a downstream config file.")
+    group.add_argument("--down-config-override", nargs="*", default=[], help="A list of key-value pairs to modify downstream config params.")
+    group = parser.add_argument_group("k-NN")
+    group.add_argument("--k", type=int, nargs="+", default=[10, 20, 100, 200], help="Neighbour counts to evaluate (each at most 256; one larger "
+                                                                                    "than the bank is dropped).")
+    group.add_argument("--temperature", type=float, default=0.07, help="Temperature of the vote's weights exp(similarity / T).")
+    group = parser.add_argument_group("Checkpointing")
+    group.add_argument("--weight-init", choices=["random", "imagenet", "torchvision", "vlinfo"], default="vlinfo",
+                       help="'random': random weights for the first evaluation; 'vlinfo': checkpoint_<start-iter>.pth of --checkpoint-dir. "
+                            "'imagenet' and 'torchvision' (model-zoo downloads) are not supported.")
+    group.add_argument("--checkpoint-dir", required=True, help="Path to load checkpoints from and write knn_acc.txt to.")
+    group.add_argument("--freq", type=int, default=46200, help="Evaluate every these many iterations.")
+    group.add_argument("--start-iter", type=int, default=46200, help="First iteration to evaluate.")
+    return parser
+
+
+def _check_knn_launch(_A):
+    from . import hip
+    if _A.num_gpus_per_machine == 0:
+        raise SystemExit("knn_clf: feature extraction and the k-NN kernels run on the MI355X only; there is no CPU path (--num-gpus-per-machine 1)")
+    if _A.num_gpus_per_machine > 1 or _A.num_machines > 1:
+        raise SystemExit("knn_clf: runs on one GPU (--num-gpus-per-machine 1)")
+    if _A.weight_init in ("imagenet", "torchvision"):
+        raise SystemExit(f"knn_clf: --weight-init {_A.weight_init} needs torchvision model-zoo downloads, which are not supported here; use random "
+                         "or vlinfo")
+    if not _A.k or min(_A.k) < 1 or max(_A.k) > hip.KNN_MAX_K:
+        raise SystemExit(f"knn_clf: every --k must be in [1, {hip.KNN_MAX_K}]")
+    if len(set(_A.k)) > hip.KNN_MAX_KS:
+        raise SystemExit(f"knn_clf: at most {hip.KNN_MAX_KS} different --k")
+    if not _A.temperature > 0:
+        raise SystemExit("knn_clf: --temperature must be positive")
+
+
+def _report_knn(res):
+    """One line per k, and the JSON entry {k: {"top1", "top5"}} of the iteration."""
+    for k, acc in res.items():
+        line = f"k-NN top-1 (k = {k}): {acc['top1']:.2f}"
+        if "top5" in acc:
+            line += f" | top-5: {acc['top5']:.2f}"
+        print(line)
+    return {str(k): acc for k, acc in res.items()}
+
+
+def knn_clf_main(_A):
+    """Weighted k-NN accuracy (knn.knn_eval) of every checkpoint in turn, as voc_clf.py walks them: features of the `train` split as the bank and of
+    the `val` split as the queries (image folder or the synthetic source), printed per k and merged into <checkpoint-dir>/knn_acc.txt."""
+    _check_knn_launch(_A)
+    if not torch.cuda.is_available():
+        raise SystemExit("knn_clf: no GPU visible; the kernels run on the MI355X only")
+    from .knn import knn_eval
+    device = torch.device("cuda", torch.cuda.current_device())
+    _DOWNC = Config(_A.down_config, _A.down_config_override)
+    common_setup(_DOWNC, _A, job_type="downstream")
+    _C = Config(_A.config, list(_A.config_override) + ["AMP", _DOWNC.AMP])       # the encoder's compute dtype follows the downstream config
+    train_dataset = DownstreamDatasetFactory.from_config(_DOWNC, split="train")
+    val_dataset = DownstreamDatasetFactory.from_config(_DOWNC, split="val")
+    num_classes = train_dataset.num_classes
+    bs = _DOWNC.OPTIM.BATCH_SIZE
+    loaders = [DataLoader(ds, batch_size=bs, shuffle=False, num_workers=_A.cpu_workers, pin_memory=True, collate_fn=ds.collate_fn)
+               for ds in (train_dataset, val_dataset)]
+    arch = PretrainingModelFactory.from_config(_C).to(device)
+
+    def load(path):
+        CheckpointManager(model=arch).load(path)
+
+    if _A.weight_init == "vlinfo":
+        load(checkpoint_path(_A.checkpoint_dir, _A.start_iter))
+
+    def evaluate():
+        ftr, ytr = extract_features(arch, loaders[0], device)
+        fte, yte = extract_features(arch, loaders[1], device)
+        return knn_eval(ftr, ytr.reshape(-1), fte, yte.reshape(-1), num_classes, _A.k, _A.temperature)
+
+    return run_checkpoint_loop(_A.checkpoint_dir, _A.start_iter, _A.freq, evaluate, load, filename="knn_acc.txt", report=_report_knn)
+
+
+def knn_clf_cli(argv=None):
+    return knn_clf_main(build_knn_parser().parse_args(argv))
 
 
 # ------------------------------------------------------------------------------------------------ image-text retrieval

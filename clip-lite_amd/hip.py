@@ -164,6 +164,8 @@ _SIGNATURES = {
     "clite_kmeans_assign": [_V, _I, _V, _V, _I, _I, _V, _V, _V, _V],
     "clite_kmeans_accumulate": [_V, _I, _V, _V, _I, _I, _I, _V, _V, _V, _U64, _V],
     "clite_kmeans_update": [_V, _U64, _V, _I, _I, _I, _V, _I, _V, _V],
+    "clite_knn_topk_merge": [_V, _I, _I, _I, _I, _I, _I, _V, _V, _V],
+    "clite_knn_vote": [_V, _V, _V, _I, _I, _I, _I, _V, _I, _F, _V, _V, _V],
     "clite_augment_gray_mean": [_V, _V, C.c_int64, _V, _I, _I, _V, _V, _V, _V, _V],
     "clite_augment_apply": [_I, _I, _V, _V, C.c_int64, _V, _V, _I, _I, _V, _I, _I, _I, _V, _V, _V],
     "clite_augment_apply_post": [_I, _I, _V, _V, C.c_int64, _V, _V, _V, _I, _I, _V, _I, _I, _I, _V, _V, _V, _V],
@@ -1058,6 +1060,36 @@ def kmeans_accumulate(X, ldx, assign, dist, N, D, K, counts, inertia, work):
 def kmeans_update(work, counts, N, D, K, Cm, ldc, hc):
     """C[k] = sum_k / count_k, hc[k] = 0.5 |c_k|^2 from what kmeans_accumulate left (include/clite.h: clite_kmeans_update)."""
     check(lib().clite_kmeans_update(p(work), work.numel() * work.element_size(), p(counts), N, D, K, p(Cm), ldc, p(hc), stream_ptr(Cm)), "kmeans_update")
+
+
+# ------------------------------------------------------------------------------------------------ k-NN classification (clip_lite_amd/knn.py)
+KNN_MAX_K, KNN_MAX_CLASSES, KNN_MAX_KS, KNN_PRED = 256, 16384, 8, 5       # include/clite.h CLITE_KNN_*
+
+
+def knn_topk_merge(scores, lds, Q, Nc, base, K, have, top_s, top_i):
+    """Folds the score tile [Q][lds] of bank rows base .. base + Nc - 1 into the running lists top_s / top_i [Q][K], of which `have` entries are
+    valid (include/clite.h: clite_knn_topk_merge)."""
+    assert scores.dtype == torch.float32 and top_s.dtype == torch.float32 and top_i.dtype == torch.int32
+    assert 1 <= K <= KNN_MAX_K and 0 <= have <= K and 0 < Nc <= lds and base >= 0 and base + Nc <= 0x7fffffff
+    assert scores.numel() >= Q * lds and top_s.numel() >= Q * K and top_i.numel() >= Q * K
+    assert top_s.is_contiguous() and top_i.is_contiguous()
+    check(lib().clite_knn_topk_merge(p(scores), lds, Q, Nc, base, K, have, p(top_s), p(top_i), stream_ptr(scores)), "knn_topk_merge")
+
+
+def knn_vote(top_s, top_i, labels, Q, K, N, Cn, ks, inv_T, class_scores, pred):
+    """pred [len(ks)][Q][KNN_PRED] (and class_scores [len(ks)][Q][Cn] unless None) of the weighted vote over the lists top_s / top_i [Q][K]
+    (include/clite.h: clite_knn_vote). ks: ascending host integers in [1, K]."""
+    ks = [int(k) for k in ks]
+    nk = len(ks)
+    assert top_s.dtype == torch.float32 and top_i.dtype == torch.int32 and labels.dtype == torch.int32 and pred.dtype == torch.int32
+    assert 1 <= K <= KNN_MAX_K and 1 <= Cn <= KNN_MAX_CLASSES and 1 <= nk <= KNN_MAX_KS and N >= 1
+    assert all(1 <= k <= K for k in ks) and all(a < b for a, b in zip(ks, ks[1:]))
+    assert top_s.is_contiguous() and top_i.is_contiguous() and top_s.numel() >= Q * K and top_i.numel() >= Q * K and labels.numel() >= N
+    assert pred.is_contiguous() and pred.numel() >= nk * Q * KNN_PRED
+    assert class_scores is None or (class_scores.dtype == torch.float32 and class_scores.is_contiguous() and class_scores.numel() >= nk * Q * Cn)
+    ks_host = (C.c_int32 * nk)(*ks)
+    check(lib().clite_knn_vote(p(top_s), p(top_i), p(labels), Q, K, N, Cn, C.cast(ks_host, C.c_void_p), nk, float(inv_T), p(class_scores), p(pred),
+                               stream_ptr(top_s)), "knn_vote")
 
 
 # ------------------------------------------------------------------------------------------------ image augmentation (clip_lite_amd/augment.py)

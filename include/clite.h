@@ -633,6 +633,35 @@ int clite_kmeans_accumulate(const float* X, int ldx, const int* assign, const fl
  * cluster.py:136-139. */
 int clite_kmeans_update(const void* work, uint64_t work_bytes, const int* counts, int N, int D, int K, float* C, int ldc, float* hc, void* stream);
 
+/* ---- Weighted k-nearest-neighbour classification on frozen features (Wu et al. 2018; clip-lite_amd/knn.py). Additive to ABI v12. The similarity
+ * matrix of the queries against the bank is formed one [query block] x [bank chunk] tile at a time (clite_gemm_nt with dtype CLITE_F32) and
+ * folded into every query's running list of its K best bank rows. Order: score descending, bank index ascending among equal scores,
+ * 0.0 == -0.0: the first K of np.argsort(-s, kind="stable") over the whole bank row. No float atomics and no order that depends on scheduling:
+ * every result below is a pure function of its inputs. */
+#define CLITE_KNN_MAX_K 256
+#define CLITE_KNN_MAX_CLASSES 16384   /* the class bins of the vote live in LDS */
+#define CLITE_KNN_MAX_KS 8
+#define CLITE_KNN_PRED 5              /* predictions per query and k */
+/* scores: f32 [Q][lds], lds >= Nc; row q holds the similarities of query q to bank rows base .. base + Nc - 1. Only columns < Nc take part
+ * (padding columns may be loaded, never selected). top_s (f32) / top_i (int32) [Q][K]: the running lists, whose first `have` entries are valid
+ * and in order (`have` is the same for all rows: min(K, base) when the chunks are fed in order). On return the first min(K, have + Nc)
+ * entries hold the best of the old list and the chunk, in order; bank indices are base + column. A NaN score is never selected (a row with
+ * fewer than that many other scores ends in entries of score -inf and index INT32_MAX). One workgroup per row streams it once: a 16-byte
+ * aligned scores with lds % 4 == 0 with 16-byte loads, any other through a scalar path. Row offsets are 64-bit. Returns -1 and launches
+ * nothing for K outside [1, CLITE_KNN_MAX_K], have outside [0, K], Q <= 0, Nc <= 0, lds < Nc, base < 0, base + Nc > INT32_MAX or a null
+ * pointer. */
+int clite_knn_topk_merge(const float* scores, int lds, int Q, int Nc, int base, int K, int have, float* top_s, int* top_i, void* stream);
+/* The vote over the final lists top_s / top_i [Q][K] (every entry valid: K <= N). labels: int32 [N] (device) in [0, C). ks: int32 [nk] in HOST
+ * memory, strictly ascending, 1 <= k <= K, nk <= CLITE_KNN_MAX_KS. For every query and every k:
+ * score[c] = sum over the ranks r < k with labels[top_i[r]] == c of exp((top_s[r] - top_s[0]) * inv_T), an f32 sum in rank order (the same
+ * bits in every run; subtracting the best similarity changes no ranking and cannot overflow). pred: int32 [nk][Q][CLITE_KNN_PRED], the best
+ * classes by (score descending, class ascending); classes without a vote score 0 and take part; positions beyond C hold -1. class_scores:
+ * f32 [nk][Q][C], or NULL. The caller validates indices and labels; an index outside [0, N) or a label outside [0, C) is skipped on the
+ * device, never read through. Returns -1 and launches nothing for K outside [1, CLITE_KNN_MAX_K], C outside [1, CLITE_KNN_MAX_CLASSES], nk
+ * outside [1, CLITE_KNN_MAX_KS], ks not ascending or outside [1, K], Q <= 0, N <= 0, inv_T negative or not finite, or a null pointer. */
+int clite_knn_vote(const float* top_s, const int* top_i, const int* labels, int Q, int K, int N, int C, const int* ks, int nk, float inv_T,
+                   float* class_scores, int* pred, void* stream);
+
 /* ---- Image augmentation on the device (reference factories.py:112-160 and data/dataloader.py:186-192, which run on the CPU; semantics:
  * clip-lite_amd/augment.py). Additive to ABI v12. canvases: uint8 [N][cap], sample n an HWC image of hw[2n] x hw[2n+1] pixels packed at the front
  * of its slot (pitch 3 w); hw: int32 [N][2]; plan: f32 [N][CLITE_AUGMENT_PLAN_W], one row per view: crop box x0, y0, cw, ch in canvas pixels,
