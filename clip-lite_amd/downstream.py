@@ -1,6 +1,6 @@
 """Command lines of the downstream evaluations: `linear_clf.py` (linear probe / fine-tune, reference linear_clf.py:25-300) and `zero_shot.py`
-(reference zero_shot.py), on ImageClassifier / zero_shot_counts (classify.py); `voc_clf.py` (svm.py), `knn_clf.py` (knn.py) and `retrieval.py`
-(retrieval.py). One GPU: the reference's multi-GPU launch, hipGraph capture of the classification step, and the `clip` / `imagenet`
+(reference zero_shot.py), on ImageClassifier / zero_shot_counts (classify.py); `voc_clf.py` (svm.py), `knn_clf.py` (knn.py), `logreg_clf.py`
+(logreg.py) and `retrieval.py` (retrieval.py). One GPU: the reference's multi-GPU launch, hipGraph capture of the classification step, and the `clip` / `imagenet`
 initialisations (the `clip` package, torchvision downloads) are not available."""
 import argparse
 import os
@@ -424,6 +424,97 @@ def knn_clf_main(_A):
 
 def knn_clf_cli(argv=None):
     return knn_clf_main(build_knn_parser().parse_args(argv))
+
+
+# ------------------------------------------------------------------------------------------------ logistic-regression probe
+def build_logreg_parser():
+    parser = common_parser(description="Logistic-regression probe (multinomial, fitted to convergence, cost chosen on a hold-out part of the "
+                                       "train split) on the frozen features of a pretrained model.")
+    parser.set_defaults(num_gpus_per_machine=1)
+    group = parser.add_argument_group("Downstream config arguments.")
+    group.add_argument("--down-config", metavar="FILE", help="Path to a downstream config file.")
+    group.add_argument("--down-config-override", nargs="*", default=[], help="A list of key-value pairs to modify downstream config params.")
+    group = parser.add_argument_group("Logistic regression")
+    group.add_argument("--cost", type=float, nargs="+", default=[1.0, 10.0, 100.0, 1000.0],
+                       help="Costs C of f(W) = 1/2 |W|^2 + C sum_i loss_i to choose from (the features are L2-normalised, so useful costs are large).")
+    group.add_argument("--holdout", type=float, default=0.1, help="Fraction of every class's train rows (its last ones) held out to choose the cost.")
+    group.add_argument("--tol", type=float, default=1e-5, help="Stop at |grad f(W)| <= tol |grad f(0)|.")
+    group = parser.add_argument_group("Checkpointing")
+    group.add_argument("--weight-init", choices=["random", "imagenet", "torchvision", "vlinfo"], default="vlinfo",
+                       help="'random': random weights for the first evaluation; 'vlinfo': checkpoint_<start-iter>.pth of --checkpoint-dir. "
+                            "'imagenet' and 'torchvision' (model-zoo downloads) are not supported.")
+    group.add_argument("--checkpoint-dir", required=True, help="Path to load checkpoints from and write logreg_acc.txt to.")
+    group.add_argument("--freq", type=int, default=46200, help="Evaluate every these many iterations.")
+    group.add_argument("--start-iter", type=int, default=46200, help="First iteration to evaluate.")
+    return parser
+
+
+def _check_logreg_launch(_A):
+    import math
+    if _A.num_gpus_per_machine == 0:
+        raise SystemExit("logreg_clf: feature extraction and the solver's kernels run on the MI355X only; there is no CPU path "
+                         "(--num-gpus-per-machine 1)")
+    if _A.num_gpus_per_machine > 1 or _A.num_machines > 1:
+        raise SystemExit("logreg_clf: runs on one GPU (--num-gpus-per-machine 1)")
+    if _A.weight_init in ("imagenet", "torchvision"):
+        raise SystemExit(f"logreg_clf: --weight-init {_A.weight_init} needs torchvision model-zoo downloads, which are not supported here; use "
+                         "random or vlinfo")
+    if not _A.cost or any(not (c > 0 and math.isfinite(c)) for c in _A.cost):
+        raise SystemExit("logreg_clf: every --cost must be positive and finite")
+    if len(set(_A.cost)) != len(_A.cost):
+        raise SystemExit("logreg_clf: --cost holds a value twice")
+    if not 0 < _A.holdout < 1:
+        raise SystemExit("logreg_clf: --holdout must be in (0, 1)")
+    if not (_A.tol > 0 and math.isfinite(_A.tol)):
+        raise SystemExit("logreg_clf: --tol must be positive")
+
+
+def _report_logreg(res):
+    """The probe's line, and the JSON entry {"cost", "top1", "top5", "holdout_top1": {cost: top-1}} of the iteration."""
+    line = f"Logistic-regression probe top-1: {res['top1']:.2f}"
+    if "top5" in res:
+        line += f" | top-5: {res['top5']:.2f}"
+    print(line + f" (cost {res['cost']:g})")
+    return {"cost": res["cost"], "top1": res["top1"], "top5": res.get("top5"), "holdout_top1": {f"{c:g}": a for c, a in res["holdout_top1"].items()}}
+
+
+def logreg_clf_main(_A):
+    """The logistic-regression probe (logreg.logreg_eval) of every checkpoint in turn, as knn_clf.py walks them: features of the `train` split to
+    fit on and of the `val` split to report on (image folder or the synthetic source), printed and merged into <checkpoint-dir>/logreg_acc.txt."""
+    _check_logreg_launch(_A)
+    _DOWNC = Config(_A.down_config, _A.down_config_override)
+    if "voc" in DownstreamDatasetFactory.dataset_name(_DOWNC.DATA.ROOT).lower():
+        raise SystemExit("logreg_clf: a VOC2007 root is multi-label, which a multinomial probe does not fit; evaluate it with voc_clf.py")
+    if not torch.cuda.is_available():
+        raise SystemExit("logreg_clf: no GPU visible; the kernels run on the MI355X only")
+    from .logreg import logreg_eval
+    device = torch.device("cuda", torch.cuda.current_device())
+    common_setup(_DOWNC, _A, job_type="downstream")
+    _C = Config(_A.config, list(_A.config_override) + ["AMP", _DOWNC.AMP])       # the encoder's compute dtype follows the downstream config
+    train_dataset = DownstreamDatasetFactory.from_config(_DOWNC, split="train")
+    val_dataset = DownstreamDatasetFactory.from_config(_DOWNC, split="val")
+    num_classes = train_dataset.num_classes
+    bs = _DOWNC.OPTIM.BATCH_SIZE
+    loaders = [DataLoader(ds, batch_size=bs, shuffle=False, num_workers=_A.cpu_workers, pin_memory=True, collate_fn=ds.collate_fn)
+               for ds in (train_dataset, val_dataset)]
+    arch = PretrainingModelFactory.from_config(_C).to(device)
+
+    def load(path):
+        CheckpointManager(model=arch).load(path)
+
+    if _A.weight_init == "vlinfo":
+        load(checkpoint_path(_A.checkpoint_dir, _A.start_iter))
+
+    def evaluate():
+        ftr, ytr = extract_features(arch, loaders[0], device)
+        fte, yte = extract_features(arch, loaders[1], device)
+        return logreg_eval(ftr, ytr.reshape(-1), fte, yte.reshape(-1), num_classes, _A.cost, _A.holdout, tol=_A.tol)
+
+    return run_checkpoint_loop(_A.checkpoint_dir, _A.start_iter, _A.freq, evaluate, load, filename="logreg_acc.txt", report=_report_logreg)
+
+
+def logreg_clf_cli(argv=None):
+    return logreg_clf_main(build_logreg_parser().parse_args(argv))
 
 
 # ------------------------------------------------------------------------------------------------ image-text retrieval

@@ -166,6 +166,14 @@ _SIGNATURES = {
     "clite_kmeans_update": [_V, _U64, _V, _I, _I, _I, _V, _I, _V, _V],
     "clite_knn_topk_merge": [_V, _I, _I, _I, _I, _I, _I, _V, _V, _V],
     "clite_knn_vote": [_V, _V, _V, _I, _I, _I, _I, _V, _I, _F, _V, _V, _V],
+    "clite_logreg_softmax": [_V, _V, _V, _V, _I, _I, _I, _I, _V, _V, _V, _V, _V],
+    "clite_logreg_hess_apply": [_V, _V, _V, _I, _I, _I, _I, _V, _V],
+    "clite_logreg_newton_begin": [_V, _I, _I, _I, _V, _V, _V, _V, _F, _I, _F, _I, _V],
+    "clite_logreg_cg_update": [_V, _I, _I, _I, _V, _V, _V, _V, _V],
+    "clite_logreg_ray_begin": [_V, _V, _V, _I, _I, _I, _V, _V],
+    "clite_logreg_ray_eval": [_V, _V, _V, _V, _V, _I, _I, _I, _I, _V, _V, _V],
+    "clite_logreg_ray_step": [_V, _I, _I, _V, _I, _V],
+    "clite_logreg_ray_finish": [_V, _V, _I, _I, _I, _V, _V],
     "clite_augment_gray_mean": [_V, _V, C.c_int64, _V, _I, _I, _V, _V, _V, _V, _V],
     "clite_augment_apply": [_I, _I, _V, _V, C.c_int64, _V, _V, _I, _I, _V, _I, _I, _I, _V, _V, _V],
     "clite_augment_apply_post": [_I, _I, _V, _V, C.c_int64, _V, _V, _V, _I, _I, _V, _I, _I, _I, _V, _V, _V, _V],
@@ -1090,6 +1098,47 @@ def knn_vote(top_s, top_i, labels, Q, K, N, Cn, ks, inv_T, class_scores, pred):
     ks_host = (C.c_int32 * nk)(*ks)
     check(lib().clite_knn_vote(p(top_s), p(top_i), p(labels), Q, K, N, Cn, C.cast(ks_host, C.c_void_p), nk, float(inv_T), p(class_scores), p(pred),
                                stream_ptr(top_s)), "knn_vote")
+
+
+# ------------------------------------------------------------------------------------------------ logistic-regression probe (clip_lite_amd/logreg.py)
+LOGREG_STATE, LOGREG_ROWS, LOGREG_MAX_CLASSES = 24, 32, 4096              # include/clite.h CLITE_LOGREG_*
+
+
+def logreg_blocks(N):
+    """Row-block partials of the row kernels (include/clite.h CLITE_LOGREG_BLOCKS)."""
+    return (N + LOGREG_ROWS - 1) // LOGREG_ROWS
+
+
+def logreg_softmax(Z, y, costs, w, N, P, Cn, ldz, Pr, S, loss, work):
+    """Pr = softmax per (row, problem) group of Z, S = c w (Pr - onehot(y)), loss[p] = sum c w (lse - z_y) (include/clite.h: clite_logreg_softmax)."""
+    assert y.dtype == torch.int32 and work.numel() >= logreg_blocks(N) * P and w.numel() >= N * P
+    check(lib().clite_logreg_softmax(p(Z), p(y), p(costs), p(w), N, P, Cn, ldz, p(Pr), p(S), p(loss), p(work), stream_ptr(Z)), "logreg_softmax")
+
+
+def logreg_hess_apply(Pr, costs, w, N, P, Cn, ldz, Q):
+    """In place q <- c w (Pr q - Pr <Pr, q>) per group (include/clite.h: clite_logreg_hess_apply)."""
+    check(lib().clite_logreg_hess_apply(p(Pr), p(costs), p(w), N, P, Cn, ldz, p(Q), stream_ptr(Q)), "logreg_hess_apply")
+
+
+def logreg_newton_begin(G, ld, n, P, X, R, D, state, tol, max_newton, eta_max, g0_only=False):
+    check(lib().clite_logreg_newton_begin(p(G), ld, n, P, p(X), p(R), p(D), p(state), tol, max_newton, eta_max, int(g0_only), stream_ptr(G)),
+          "logreg_newton_begin")
+
+
+def logreg_cg_update(HD, ld, n, P, X, R, D, state):
+    check(lib().clite_logreg_cg_update(p(HD), ld, n, P, p(X), p(R), p(D), p(state), stream_ptr(HD)), "logreg_cg_update")
+
+
+def logreg_line_search(Z, delta, y, costs, w, N, P, Cn, ldz, G, W, D, ld, n, state, work, evals=8):
+    """The whole line search along D, enqueued without a read-back: ray_begin, `evals` x (ray_eval, ray_step), ray_finish (W += t D)
+    (include/clite.h: clite_logreg_ray_*)."""
+    assert y.dtype == torch.int32 and evals >= 1 and work.numel() >= 2 * logreg_blocks(N) * P
+    l, st = lib(), stream_ptr(Z)
+    check(l.clite_logreg_ray_begin(p(G), p(W), p(D), ld, n, P, p(state), st), "logreg_ray_begin")
+    for e in range(evals):
+        check(l.clite_logreg_ray_eval(p(Z), p(delta), p(y), p(costs), p(w), N, P, Cn, ldz, p(state), p(work), st), "logreg_ray_eval")
+        check(l.clite_logreg_ray_step(p(work), N, P, p(state), int(e == evals - 1), st), "logreg_ray_step")
+    check(l.clite_logreg_ray_finish(p(W), p(D), ld, n, P, p(state), st), "logreg_ray_finish")
 
 
 # ------------------------------------------------------------------------------------------------ image augmentation (clip_lite_amd/augment.py)

@@ -662,6 +662,56 @@ int clite_knn_topk_merge(const float* scores, int lds, int Q, int Nc, int base, 
 int clite_knn_vote(const float* top_s, const int* top_i, const int* labels, int Q, int K, int N, int C, const int* ks, int nk, float inv_T,
                    float* class_scores, int* pred, void* stream);
 
+/* ---- Logistic-regression probe on frozen features (the linear-probe protocol of CLIP; clip-lite_amd/logreg.py). Additive to ABI v12. P independent
+ *   min_W f_p(W) = 1/2 |W|_F^2 + c_p sum_i w_ip (logsumexp(W x~_i) - (W x~_i)[y_i]),   W in R^{C x Dp}
+ * (sklearn LogisticRegression(C=c_p, fit_intercept=False) on the augmented rows with sample_weight w[:, p]: the bias is the last weight and is
+ * regularised) over one shared f32 matrix X~ [N][Dp], solved by batched Newton-CG: every CG iteration is clite_gemm_nt (X~ D^T) and clite_gemm_tn
+ * (Q^T X~ + D) plus the kernels below. Row operands (logits Z = X~ W^T, probabilities Pr, gradient operand S, Q, delta) are f32 [N][ldz],
+ * 16-byte aligned, ldz % 4 == 0, ldz >= P * Cp with Cp = ceil8(C): problem p owns columns p * Cp .. p * Cp + C - 1, its padding columns are
+ * written as zeros and take no part in any softmax, columns from P * Cp on are never touched. y: int32 [N] in [0, C) (validated by the caller;
+ * a label outside is never read through). costs: f32 [P]. w: f32 [N][P], w_ip >= 0, 0 holds a row out. Vectors (W, the gradient G, the CG
+ * vectors X, R, D, HD) are f32 [P * Cp][Dp]: one contiguous span of n = Cp * Dp floats per problem, `ld` floats apart (ld >= n). Per-problem
+ * scalars stay on the device in `state`, f32 [P][CLITE_LOGREG_STATE], zero-initialised with the active flag (column 9) set: 0 |grad f(0)|,
+ * 1 |grad f(W)|, 2 their ratio, 5 last step length, 6 Newton iterations, 8 CG iterations, 11 CG iterations of the previous Newton iteration,
+ * 12 phi'(0) of the last line search, 21 its evaluations. Every sum is formed in one fixed order (no float atomics): results are bitwise
+ * reproducible in either deterministic mode. Row kernels return -2 for C > CLITE_LOGREG_MAX_CLASSES (a group is held in registers) and -1 for
+ * any other bad argument (null or misaligned pointer, N, P or C <= 0, P > 65535, ldz too small); nothing is launched then. */
+#define CLITE_LOGREG_STATE 24
+#define CLITE_LOGREG_ROWS 32            /* rows per row-block partial */
+#define CLITE_LOGREG_MAX_CLASSES 4096
+#define CLITE_LOGREG_BLOCKS(N) (((N) + CLITE_LOGREG_ROWS - 1) / CLITE_LOGREG_ROWS)
+/* Pr = softmax over each group of Z, S = c_p w_ip (Pr - onehot(y_i)), loss (f32 [P]) = sum_i c_p w_ip (lse - z_y), the data term of f_p, from
+ * row-block partials summed in block order. Stable for logits of any finite magnitude (the group maximum is subtracted). work: f32
+ * [CLITE_LOGREG_BLOCKS(N)][P] scratch. The gradient is G = W + S^T X~ (clite_gemm_tn with the residual epilogue). */
+int clite_logreg_softmax(const float* Z, const int* y, const float* costs, const float* w, int N, int P, int C, int ldz, float* Pr, float* S,
+                         float* loss, float* work, void* stream);
+/* In place on Q = X~ D^T: q <- c_p w_ip (Pr * q - Pr <Pr, q>) per group (zeros in a held-out group, which is not read); then the Hessian-vector
+ * product is HD = D + Q^T X~. */
+int clite_logreg_hess_apply(const float* Pr, const float* costs, const float* w, int N, int P, int C, int ldz, float* Q, void* stream);
+/* One workgroup per problem: |G_p| and the stopping test: |G_p| <= tol |grad f_p(0)|, max_newton steps taken, or a last line search that ended at
+ * step 0 (W did not move, so the iteration would only repeat); the problem then freezes, in the last two cases with its ratio above tol. For a
+ * problem that goes on the start of a CG solve of H x = -g: X = 0, R = D = -G, CG tolerance eta |g| with eta = min(eta_max, sqrt(|g| / |g0|)).
+ * |grad f_p(0)| is what a call with g0_only = 1 recorded (G then being the gradient at W = 0; nothing else is written), else |G_p| of the first
+ * call (a cold start). */
+int clite_logreg_newton_begin(const float* G, int ld, int n, int P, float* X, float* R, float* D, float* state, float tol, int max_newton,
+                              float eta_max, int g0_only, void* stream);
+/* One CG iteration for every problem whose solve is still open: alpha = r.r / d.HD, X += alpha D, R -= alpha HD, then stop when |R| <= the
+ * tolerance or D = R + beta D. Problems that are frozen or done are left untouched. */
+int clite_logreg_cg_update(const float* HD, int ld, int n, int P, float* X, float* R, float* D, float* state, void* stream);
+/* The line search along D minimises phi_p(t) = f_p(W + t D) by safeguarded Newton on phi' inside a bracket, starting at t = 1:
+ *   phi'(t) = <W + t D, D> + c sum_i w_i (<softmax(z_i + t d_i), d_i> - d_i[y_i]),   phi''(t) = |D|^2 + c sum_i w_i Var_softmax(z_i + t d_i)(d_i).
+ * ray_begin: phi'(0) = <G, D>, <W, D>, |D|^2; a problem that is not active, or with phi'(0) >= 0, is done at t = 0. ray_eval: one pass over Z
+ * and delta = X~ D^T (the padding columns of both may hold anything) that writes the row-block partials of the two sums at the current t_p into work (f32 [2][CLITE_LOGREG_BLOCKS(N)][P]);
+ * finished problems are skipped. ray_step (one workgroup): sums the partials in block order and moves t_p and the bracket; the search of a
+ * problem ends at |phi'(t)| <= 1e-4 |phi'(0)|, at a step that no longer moves t, or with last != 0 (then at the bracket's left end lo:
+ * phi' < 0 on [0, lo], so phi(lo) <= phi(0); that is t = 0 when no point left of the minimiser was found). ray_finish: W_p += t_p D_p for every finished search. Enqueue ray_begin, a fixed number of
+ * (ray_eval, ray_step) pairs with last set on the final one, then ray_finish. */
+int clite_logreg_ray_begin(const float* G, const float* W, const float* D, int ld, int n, int P, float* state, void* stream);
+int clite_logreg_ray_eval(const float* Z, const float* delta, const int* y, const float* costs, const float* w, int N, int P, int C, int ldz,
+                          const float* state, float* work, void* stream);
+int clite_logreg_ray_step(const float* work, int N, int P, float* state, int last, void* stream);
+int clite_logreg_ray_finish(float* W, const float* D, int ld, int n, int P, const float* state, void* stream);
+
 /* ---- Image augmentation on the device (reference factories.py:112-160 and data/dataloader.py:186-192, which run on the CPU; semantics:
  * clip-lite_amd/augment.py). Additive to ABI v12. canvases: uint8 [N][cap], sample n an HWC image of hw[2n] x hw[2n+1] pixels packed at the front
  * of its slot (pitch 3 w); hw: int32 [N][2]; plan: f32 [N][CLITE_AUGMENT_PLAN_W], one row per view: crop box x0, y0, cw, ch in canvas pixels,
