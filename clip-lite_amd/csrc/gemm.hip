@@ -420,8 +420,7 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(const float* __restr
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = relu_f(v[e]);
       } else if (ep.act == CLITE_ACT_GELU) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = gelu_t<T>(v[e]);
+        gelu8_t<T>(v);
       } else if (ep.act == CLITE_ACT_TANH) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = tanhf(v[e]);
@@ -429,8 +428,15 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(const float* __restr
       if (ep.dact_aux) {
         float a[8];
         load8((const T*)ep.dact_aux + o, a);
+        float d[8];
+        if (ep.dact == 2) {
+          gelu_grad8_t<T>(a, d);
+        } else {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] *= ep.dact == 1 ? (a[e] > 0.f ? 1.f : 0.f) : ep.dact == 2 ? gelu_grad_t<T>(a[e]) : (1.f - a[e] * a[e]);
+          for (int e = 0; e < 8; ++e) d[e] = ep.dact == 1 ? (a[e] > 0.f ? 1.f : 0.f) : (1.f - a[e] * a[e]);
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) v[e] *= d[e];
       }
       if (ep.residual) {
         float rv[8];

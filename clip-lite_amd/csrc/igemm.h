@@ -76,31 +76,63 @@ DEV float gelu_grad_f(float x) {
 // (Round 4: constants folded — 1 / (1 + p |x| / sqrt 2), e^(-x^2 / 2) as exp2 of ONE product, the 0.5 inside the coefficients — and the sign
 // select replaced by arithmetic: with h = 0.5 erfc(|x| / sqrt 2), x Phi(x) = max(x, 0) - |x| h. 13 / 16 instructions per element instead of 18 / 21:
 // at one 8-wave workgroup per CU the GELU launches' epilogue is VALU-bound, 128 elements per thread.)
+// (The tail: 7.1.26 bounds the ABSOLUTE error, and below x = -5 the values themselves are smaller than that — its relative error reaches 3 %, and
+// 0.5 - (0.5 - h) loses h altogether: up to 8 bf16 ulps in a stored GELU' of 1e-6. TAIL swaps in a fit of Phi(-a) e^(a^2 / 2) over a = 4.5 .. 14 in the
+// same t, relative error 6e-6, and takes Phi(x) = h directly. gelu8_t / gelu_grad8_t below pay one min-of-8 and one branch for it: the tail is
+// recomputed only where one of a thread's eight inputs lies below GELU_TAIL_X, which activations of a trained or freshly initialised FFN do not.
+// The branch splits the unrolled rows: at M = 3840 FFN1 forward went 36.7 -> 39.5 us and FFN2's input gradient 40.0 -> 40.4 us, 0.25 % of the step.)
+constexpr float GELU_TAIL_X = -5.0f;
+template <bool TAIL = false>
 DEV void gelu_fast_parts(float x, float& half_erfc, float& gauss) {
   const float ax = fabsf(x);
   const float t = __frcp_rn(__fmaf_rn(0.3275911f * 0.70710678118654752f, ax, 1.0f));
   gauss = __builtin_amdgcn_exp2f((x * x) * (-0.5f * 1.4426950408889634f));          // e^(-x^2 / 2)
-  const float poly = ((((0.5f * 1.061405429f * t - 0.5f * 1.453152027f) * t + 0.5f * 1.421413741f) * t - 0.5f * 0.284496736f) * t + 0.5f * 0.254829592f) * t;
+  const float poly = TAIL ? ((((0.22693126f * t - 0.058025274f) * t + 0.13806723f) * t + 0.083405286f) * t + 0.093033388f) * t
+                          : ((((0.5f * 1.061405429f * t - 0.5f * 1.453152027f) * t + 0.5f * 1.421413741f) * t - 0.5f * 0.284496736f) * t + 0.5f * 0.254829592f) * t;
   half_erfc = poly * gauss;            // 0.5 * erfc(|x| / sqrt 2) = Phi(-|x|)
 }
-template <typename T> DEV float gelu_t(float x) {
+template <typename T, bool TAIL = false> DEV float gelu_t(float x) {
   if constexpr (sizeof(T) == 2) {
     float h, g;
-    gelu_fast_parts(x, h, g);
+    gelu_fast_parts<TAIL>(x, h, g);
     return __fmaf_rn(-fabsf(x), h, fmaxf(x, 0.f));          // x >= 0: x (1 - h); x < 0: x h  (a NaN stays a NaN through the product)
   } else {
     return gelu_f(x);
   }
 }
-template <typename T> DEV float gelu_grad_t(float x) {
+template <typename T, bool TAIL = false> DEV float gelu_grad_t(float x) {
   if constexpr (sizeof(T) == 2) {
     float h, g;
-    gelu_fast_parts(x, h, g);
-    const float cdf = 0.5f + copysignf(0.5f - h, x);          // Phi(x) = 1 - h for x >= 0, h for x < 0
+    gelu_fast_parts<TAIL>(x, h, g);
+    const float cdf = TAIL ? h : 0.5f + copysignf(0.5f - h, x);          // Phi(x) = 1 - h for x >= 0, h for x < 0 (TAIL: x < 0)
     return __fmaf_rn(x * 0.39894228040143268f, g, cdf);
   } else {
     return gelu_grad_f(x);
   }
+}
+DEV float min8(const float (&v)[8]) { return fminf(fminf(fminf(v[0], v[1]), fminf(v[2], v[3])), fminf(fminf(v[4], v[5]), fminf(v[6], v[7]))); }
+// v[e] = GELU(v[e]) / d[e] = GELU'(a[e]) for a thread's eight elements
+template <typename T> DEV void gelu8_t(float (&v)[8]) {
+  if constexpr (sizeof(T) == 2) {
+    if (min8(v) < GELU_TAIL_X) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[e] = v[e] < GELU_TAIL_X ? gelu_t<T, true>(v[e]) : gelu_t<T>(v[e]);
+      return;
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) v[e] = gelu_t<T>(v[e]);
+}
+template <typename T> DEV void gelu_grad8_t(const float (&a)[8], float (&d)[8]) {
+  if constexpr (sizeof(T) == 2) {
+    if (min8(a) < GELU_TAIL_X) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) d[e] = a[e] < GELU_TAIL_X ? gelu_grad_t<T, true>(a[e]) : gelu_grad_t<T>(a[e]);
+      return;
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) d[e] = gelu_grad_t<T>(a[e]);
 }
 
 // Optional remap of GEMM rows to rows of the output (and of the residual / aux tensors): GEMM row p = (n, ho, wo) over an
@@ -261,8 +293,7 @@ DEV void igemm_epilogue(f32x16 (&acc)[CFG::RM][CFG::RN], const Epilogue& ep, con
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = relu_f(v[e]);
       } else if (ep.act == ACT_GELU) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = gelu_t<T>(v[e]);
+        gelu8_t<T>(v);
       } else if (ep.act == ACT_TANH) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = tanhf(v[e]);
@@ -271,10 +302,11 @@ DEV void igemm_epilogue(f32x16 (&acc)[CFG::RM][CFG::RN], const Epilogue& ep, con
       if (ep.dact_aux) {
         float av[8];
         if constexpr (HEAVY) pa[q].get(av); else load8((const T*)ep.dact_aux + gidx, av);
+        if (ep.dact == 2) {
+          gelu_grad8_t<T>(av, dfac);
+        } else {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          float a = av[e];
-          dfac[e] = ep.dact == 1 ? (a > 0.f ? 1.f : 0.f) : ep.dact == 2 ? gelu_grad_t<T>(a) : (1.f - a * a);
+          for (int e = 0; e < 8; ++e) dfac[e] = ep.dact == 1 ? (av[e] > 0.f ? 1.f : 0.f) : (1.f - av[e] * av[e]);
         }
         if (!HEAVY || !ep.mask_after_residual) {
 #pragma unroll

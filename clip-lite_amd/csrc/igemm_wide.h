@@ -299,8 +299,7 @@ DEV void wide_epilogue(f32x16 (&acc)[CFG::RM][CFG::RN], const Epilogue& ep, cons
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = relu_f(v[e]);
       } else if (act == ACT_GELU) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) v[e] = gelu_t<T>(v[e]);
+        gelu8_t<T>(v);
       } else if (act == ACT_TANH) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = tanhf(v[e]);
@@ -314,10 +313,11 @@ DEV void wide_epilogue(f32x16 (&acc)[CFG::RM][CFG::RN], const Epilogue& ep, cons
       } else if (has_aux) {
         float av[8];
         pa[it].get(av);
+        if (dact == 2) {
+          gelu_grad8_t<T>(av, dfac);
+        } else {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) {
-          const float a = av[e];
-          dfac[e] = dact == 1 ? (a > 0.f ? 1.f : 0.f) : dact == 2 ? gelu_grad_t<T>(a) : (1.f - a * a);
+          for (int e = 0; e < 8; ++e) dfac[e] = dact == 1 ? (av[e] > 0.f ? 1.f : 0.f) : (1.f - av[e] * av[e]);
         }
       }
       if ((has_bits || has_aux) && !mask_after) {
