@@ -13,7 +13,11 @@ namespace {
 
 constexpr int XU = 4;                       // 4-column chunks in flight per lane per iteration
 
-// Online max / sum-of-exp of one lane's columns: (m, s) with s = sum exp(z - m). An empty lane keeps m = -inf, s = 0.
+// Online max / sum-of-exp of one lane's columns: (m, s) with s = sum exp(z - m). A lane starts, and an empty lane stays, at m = LSE_EMPTY, s = 0:
+// the most negative FINITE float, not -inf, so that an element at -inf (a masked class, which nn.CrossEntropyLoss accepts anywhere but at the
+// label) takes the second branch as exp(-inf - m) = 0 and contributes nothing; from m = -inf that difference was NaN. The first finite
+// element replaces the start value through s = 0 * exp(m - v) + 1 = 1, and a logit equal to LSE_EMPTY itself adds exp(0) = 1 as it should.
+constexpr float LSE_EMPTY = -3.402823466e+38f;
 DEV void lse_merge(float& m, float& s, float v) {
   if (v > m) {
     s = s * expf(m - v) + 1.f;
@@ -35,7 +39,7 @@ __global__ __launch_bounds__(64) void xent_fwd_kernel(const float* z, int ld, in
     const bool valid = y64 >= 0 && y64 < C;
     const int y = valid ? (int)y64 : 0;
     const float zy = valid ? row[y] : 0.f;
-    float m = -INFINITY, s = 0.f, rank = 0.f;
+    float m = LSE_EMPTY, s = 0.f, rank = 0.f;
     for (int j0 = lane * 4; j0 < C; j0 += 64 * 4 * XU) {
       f32x4 v[XU];
 #pragma unroll
@@ -57,7 +61,7 @@ __global__ __launch_bounds__(64) void xent_fwd_kernel(const float* z, int ld, in
       }
     }
     const float M = wave_max(m);
-    s = m == -INFINITY ? 0.f : s * expf(m - M);
+    s = s * expf(m - M);                       // an empty or fully masked lane: s = 0 times a factor in [0, 1]
     const float S = wave_sum(s);
     const float r = wave_sum(rank);
     const float l = M + logf(S);

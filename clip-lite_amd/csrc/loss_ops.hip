@@ -90,21 +90,29 @@ __global__ __launch_bounds__(256) void l2_normalize_kernel(const T* x, T* out, i
 // C[i][j] = <a_i, b_j> the cosines of the L2-normalised projections, t = exp(temperature), targets on the diagonal):
 //   L = 1/(2B) * [ sum_i (lse_j S[i][j] - S[i][i]) + sum_j (lse_i S[i][j] - S[j][j]) ].
 // One wave per line (row: sr = ld, se = 1; column: sr = 1, se = ld); lse[line] kept for backward; acc += sum (lse - S_diag) / (2B).
+// S[i][j] is the ROUNDED f32 product t * C[i][j] at every use, in both kernels: lse is built from the rounded values (the max pass cannot fuse its
+// product), so a later t * C - lse that the compiler contracts into one fma sees a different S. Near a sharp diagonal (S ~ 60 at t = 100, half an
+// ulp = 1.9e-6) softmax_row + softmax_col - 2 cancels down to 1e-4 and that half ulp became a few percent of dC[i][i]; with the same S on both
+// sides the difference S[i][i] - lse[i] is exact.
+DEV float scaled(float t, float c) {
+#pragma clang fp contract(off)
+  return t * c;
+}
 __global__ __launch_bounds__(256) void infonce_lse_kernel(const float* Cm, int sr, int se, int B, const float* temperature, float* lse, float* acc) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const float t = expf(temperature[0]);
   for (int i = blockIdx.x * (blockDim.x >> 6) + wave; i < B; i += gridDim.x * (blockDim.x >> 6)) {
     const float* line = Cm + (size_t)i * sr;
     float m = -INFINITY;
-    for (int j = lane; j < B; j += 64) m = fmaxf(m, t * line[(size_t)j * se]);
+    for (int j = lane; j < B; j += 64) m = fmaxf(m, scaled(t, line[(size_t)j * se]));
     m = wave_max(m);
     float s = 0.f;
-    for (int j = lane; j < B; j += 64) s += expf(t * line[(size_t)j * se] - m);
+    for (int j = lane; j < B; j += 64) s += expf(scaled(t, line[(size_t)j * se]) - m);
     s = wave_sum(s);
     float l = m + logf(s);
     if (lane == 0) {
       lse[i] = l;
-      atomic_add_f32(acc, (l - t * line[(size_t)i * se]) / (2.0f * (float)B));
+      atomic_add_f32(acc, (l - scaled(t, line[(size_t)i * se])) / (2.0f * (float)B));
     }
   }
 }
@@ -125,7 +133,7 @@ __global__ __launch_bounds__(256) void infonce_bwd_kernel(const float* Cm, int l
         int j = j0 + e;
         float v = 0.f;
         if (j < B) {
-          float sij = t * Cm[(size_t)i * ld + j];
+          float sij = scaled(t, Cm[(size_t)i * ld + j]);
           float d = g * (expf(sij - lr) + expf(sij - lse_c[j]) - (i == j ? 2.f : 0.f));
           dt += d * sij;
           v = d * t;

@@ -5,6 +5,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from loss_ref import MASKED_ROW, xent_reference as _reference
 from simlib import lib, outbuf, ptr, val
 
 BF16, F32 = 0, 1
@@ -16,31 +17,6 @@ def _bind():
     L.clite_xent_bwd.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                  C.c_void_p, C.c_int, C.c_void_p]
     return L
-
-
-def _reference(z, y, topk):
-    """float64: per-row lse, mean loss over counted rows, top-1 / top-k counts with ties to the lower index, count, dlogits/gout."""
-    z = z.astype(np.float64)
-    B, Cc = z.shape
-    m = z.max(1, keepdims=True)
-    lse = (np.log(np.exp(z - m).sum(1, keepdims=True)) + m)[:, 0]
-    ok = (y >= 0) & (y < Cc)
-    n = int(ok.sum())
-    loss = top1 = topk_n = 0.0
-    d = np.zeros_like(z)
-    for i in range(B):
-        if not ok[i]:
-            continue
-        zy = z[i, y[i]]
-        rank = int((z[i] > zy).sum() + (z[i, :y[i]] == zy).sum())
-        loss += lse[i] - zy
-        top1 += rank == 0
-        topk_n += rank < topk
-        d[i] = np.exp(z[i] - lse[i])
-        d[i, y[i]] -= 1.0
-    if n:
-        d /= n
-    return lse, loss, top1, topk_n, n, d
 
 
 def _run(L, z, ld, y, topk, Bp, ldd, dtype, gout=0.7):
@@ -137,3 +113,33 @@ def test_xent_deterministic_mode_repeats_bitwise():
         assert np.array_equal(a.view(np.uint32), b.view(np.uint32))
     rl, rloss, _, _, rn, _ = _reference(z, y, 5)
     assert runs[0][1][3] == rn and abs(runs[0][1][0] - rloss) < 1e-5 * rloss
+
+
+@pytest.mark.parametrize("dtype", [BF16, F32])
+def test_xent_masked_classes_contribute_nothing(dtype):
+    """nn.CrossEntropyLoss with a class at -inf that is not the label: a finite loss, nothing from that class, gradient exactly 0 there. The first
+    row starts a lane with -inf before any finite value; the others have one behind finite values, in other lanes' first columns, in a second
+    trip of the column loop, and in every class but the label."""
+    L = _bind()
+    z, y, want = MASKED_ROW
+    lse, acc, dz = _run(L, z, 8, y, 1, 8, 8, dtype)
+    assert abs(lse[0] - want) < 1e-5 and abs(acc[0] - (want - 2.0)) < 1e-5 and acc[1] == 0 and acc[3] == 1
+    rng = np.random.default_rng(5)
+    B, Cc = 6, 1030
+    z = (rng.standard_normal((B, Cc)) * 3).astype(np.float32)
+    y = np.array([0, 5, 1029, 300, 7, 4])
+    z[0, 1] = -np.inf                       # behind a finite value in lane 0
+    z[1, 0:1024:4] = -np.inf                # the first column of every lane's every chunk
+    z[2, 1024:1029] = -np.inf               # lanes 0 and 1 in the second trip of the 1024-column loop
+    z[3, :300] = z[3, 301:] = -np.inf       # every class but the label
+    z[4, rng.choice(np.setdiff1d(np.arange(Cc), [7]), 400, replace=False)] = -np.inf
+    lse, acc, dz = _run(L, z, 1032, y, 5, 16, 1032, dtype)
+    rl, rloss, rt1, rtk, rn, rd = _reference(z, y, 5)
+    assert np.isfinite(lse).all() and np.abs(lse - rl).max() < 1e-4 * max(1.0, np.abs(rl).max())
+    assert acc[3] == rn and acc[1] == rt1 and acc[2] == rtk
+    assert abs(acc[0] - rloss) < 1e-5 * max(1.0, abs(rloss))
+    got = dz[:B, :Cc]
+    tol = 1e-2 if dtype == BF16 else 1e-5
+    assert np.abs(got - 0.7 * rd).max() <= tol * np.abs(0.7 * rd).max()
+    assert not got[np.isneginf(z)].any()
+    assert not dz[B:].any() and not dz[:, Cc:].any()
