@@ -41,6 +41,27 @@ struct GroupItem {
 };
 struct WgEntry { uint32_t item, tile_m, tile_n, kchunk; };      // one per workgroup
 
+// The ring's DMA in the grouped kernels goes out in the form the compiler does not model (buf_load16_lds_untracked, intrin.h). Both operands are XC
+// images read through ds_read_b64_tr_*; behind the builtin form of the DMA the compiler placed an `s_waitcnt vmcnt(0)` in front of the first
+// transposed read that follows the issue — it sees an LDS write and cannot tell that the read is of another stage — so the tile requested in
+// iteration t was waited for inside iteration t: DMA, fragment reads and MFMAs of a K tile ran one after another (DESIGN.md §3.1 has the loop
+// skeletons). The kernels' own protocol orders every access, so that wait protects nothing:
+//   read after write   tile t's stage is read only behind `wait_vmcnt<N>` (this wave's share of tile t has landed: loads retire in order and N
+//                      counts the younger tiles' loads, LOADS_PER_TILE each, by hand) and the `barrier_raw` that follows it (everyone's share).
+//   write after read   the DMA issued in iteration t overwrites the stage of tile t-1. A wave passes iteration t's barrier only after the MFMAs
+//                      of tile t-1, which are in front of it in program order and wait (lgkmcnt) for every fragment read of t-1 to return.
+//   compiler's waits   the loads the compiler does count (descriptors, row_scale) share the in-order vmcnt with the DMA it does not see: its
+//                      vmcnt(N) can only wait for more than it meant to, never for less.
+// -DCLITE_GROUP_DMA_TRACKED (A/B builds only) puts the builtin form back.
+template <class L> struct GroupIssue {
+#ifdef CLITE_GROUP_DMA_TRACKED
+  static constexpr bool UNTRACKED = false;
+#else
+  static constexpr bool UNTRACKED = true;
+#endif
+  DEV static void go(const L& l, typename L::State& st, char* lds, int wave, int lane, int x0) { l.template issue<UNTRACKED>(st, lds, wave, lane, x0); }
+};
+
 template <class CFG, class LA, class LB, int NSTAGE>
 __global__ __launch_bounds__(256) void igemm_group_kernel(const GroupItem<LA, LB>* __restrict__ items, const WgEntry* __restrict__ map) {
   typedef bf16 T;
@@ -89,8 +110,8 @@ __global__ __launch_bounds__(256) void igemm_group_kernel(const GroupItem<LA, LB
 #pragma unroll
   for (int pz = 0; pz < NSTAGE - 1; ++pz) {
     if (t_begin + pz < t_end) {
-      DmaIssue<LA>::go(la, sa, smem + pz * STAGE, wave, lane, m0);
-      DmaIssue<LB>::go(lb, sb, smem + pz * STAGE + LA::BYTES, wave, lane, n0);
+      GroupIssue<LA>::go(la, sa, smem + pz * STAGE, wave, lane, m0);
+      GroupIssue<LB>::go(lb, sb, smem + pz * STAGE + LA::BYTES, wave, lane, n0);
     }
   }
   int buf = 0;
@@ -108,8 +129,8 @@ __global__ __launch_bounds__(256) void igemm_group_kernel(const GroupItem<LA, LB
     for (int j = 0; j < RN; ++j) bf0[j] = LB::frag_at(bbuf + boff[j][0]);
     if (t + NSTAGE - 1 < t_end) {
       int nb = buf + NSTAGE - 1; if (nb >= NSTAGE) nb -= NSTAGE;
-      DmaIssue<LA>::go(la, sa, smem + nb * STAGE, wave, lane, m0);
-      DmaIssue<LB>::go(lb, sb, smem + nb * STAGE + LA::BYTES, wave, lane, n0);
+      GroupIssue<LA>::go(la, sa, smem + nb * STAGE, wave, lane, m0);
+      GroupIssue<LB>::go(lb, sb, smem + nb * STAGE + LA::BYTES, wave, lane, n0);
     }
 #pragma unroll
     for (int ks = 0; ks < BK / 16; ++ks) {
@@ -158,7 +179,11 @@ __global__ __launch_bounds__(256) void igemm_group_kernel(const GroupItem<LA, LB
 
 // The same grouped launch on the 8-wave wide tiles of igemm_wide.h (K tile 64, one workgroup per CU): a 256 x 256 tile stages 256 B of
 // operands per MFMA, 256 x 128 / 128 x 256 384 B, the 4-wave 128 x 128 x 32 tile 512 B — and the weight-gradient GEMMs (K = 3840 ... 25088
-// pixels or tokens) are bound by exactly that L2 -> LDS traffic (500-620 TF/s on the narrow tiles). Members whose output
+// pixels or tokens) move more L2 -> LDS bytes per MFMA than any other GEMM of the step (500-620 TF/s on the narrow tiles). That traffic was long
+// read as their bound; it was not: a K tile's DMA (0.74 us), its transposed fragment reads (0.6-0.8 us) and its MFMAs (1.41 us) ran one after
+// another behind a compiler-inserted vmcnt(0) (GroupIssue above), and their SUM was the measured 2.7-3.2 us per K tile. With the DMA overlapped the
+// BERT group runs at ~2.3 us per K tile (982 -> 828 us per launch; DESIGN.md §3.1, profiles/group_ring_ab.txt): what is left over the MFMA time is
+// the fragment reads, which the 2-stage ring's single barrier per tile still exposes. Members whose output
 // has >= 256 rows and columns (every BERT matrix, the layer3 / layer4 convs) take the 256 x 256 tile; narrower outputs (layer1, layer2) stay on
 // the 4-wave kernels above. Both operands are XC images (contraction index slow).
 template <class CFG, class LA, class LB, int NSTAGE>
@@ -207,8 +232,8 @@ __global__ __launch_bounds__(512) void igemm_group_wide_kernel(const GroupItem<L
 #pragma unroll
   for (int pz = 0; pz < NSTAGE - 1; ++pz) {
     if (t_begin + pz < t_end) {
-      WideIssue<LA>::go(la, sa, smem + pz * STAGE, wave, lane, m0);
-      WideIssue<LB>::go(lb, sb, smem + pz * STAGE + LA::BYTES, wave, lane, n0);
+      GroupIssue<LA>::go(la, sa, smem + pz * STAGE, wave, lane, m0);
+      GroupIssue<LB>::go(lb, sb, smem + pz * STAGE + LA::BYTES, wave, lane, n0);
     }
   }
   int buf = 0;
@@ -226,8 +251,8 @@ __global__ __launch_bounds__(512) void igemm_group_wide_kernel(const GroupItem<L
     for (int j = 0; j < RN; ++j) bf0[j] = LB::frag_at(bbuf + boff[j][0]);
     if (t + NSTAGE - 1 < t_end) {
       int nb = buf + NSTAGE - 1; if (nb >= NSTAGE) nb -= NSTAGE;
-      WideIssue<LA>::go(la, sa, smem + nb * STAGE, wave, lane, m0);
-      WideIssue<LB>::go(lb, sb, smem + nb * STAGE + LA::BYTES, wave, lane, n0);
+      GroupIssue<LA>::go(la, sa, smem + nb * STAGE, wave, lane, m0);
+      GroupIssue<LB>::go(lb, sb, smem + nb * STAGE + LA::BYTES, wave, lane, n0);
     }
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
@@ -331,8 +356,8 @@ __global__ __launch_bounds__(512) void igemm_group_fp8_kernel(const GroupItem<LA
 #pragma unroll
   for (int pz = 0; pz < NSTAGE - 1; ++pz) {
     if (t_begin + pz < t_end) {
-      WideIssue<LA>::go(la, sa, smem + pz * STAGE, wave, lane, m0);
-      WideIssue<LB>::go(lb, sb, smem + pz * STAGE + LA::BYTES, wave, lane, n0);
+      GroupIssue<LA>::go(la, sa, smem + pz * STAGE, wave, lane, m0);
+      GroupIssue<LB>::go(lb, sb, smem + pz * STAGE + LA::BYTES, wave, lane, n0);
     }
   }
   int buf = 0;
@@ -360,8 +385,8 @@ __global__ __launch_bounds__(512) void igemm_group_fp8_kernel(const GroupItem<LA
     }
     if (t + NSTAGE - 1 < t_end) {
       int nb = buf + NSTAGE - 1; if (nb >= NSTAGE) nb -= NSTAGE;
-      WideIssue<LA>::go(la, sa, smem + nb * STAGE, wave, lane, m0);
-      WideIssue<LB>::go(lb, sb, smem + nb * STAGE + LA::BYTES, wave, lane, n0);
+      GroupIssue<LA>::go(la, sa, smem + nb * STAGE, wave, lane, m0);
+      GroupIssue<LB>::go(lb, sb, smem + nb * STAGE + LA::BYTES, wave, lane, n0);
     }
 #pragma unroll
     for (int i = 0; i < RM; ++i)
@@ -439,6 +464,9 @@ typedef DmaXCGather<bf16, 256, WIDE_BK, WIDE_NW> WG256;
 typedef DmaXCStrided<uint8_t, 256, WIDE_BK, WIDE_NW> FS256;          // fp8 operand images: [64 pixels][256 channels x 1 B]
 typedef DmaXCGather<uint8_t, 256, WIDE_BK, WIDE_NW> FG256;
 constexpr int WKCHUNK = 128;            // K tiles of 64 per workgroup at most (8192 pixels / tokens, as KCHUNK)
+// (Re-measured with the ring's overlap restored: a 4-stage ring on the 4-wave groups takes 1540 instead of 1605 us per launch of the ResNet group
+// but leaves the step where it was, 14.37 against 14.37 ms in B C .. C B order — 64 KB of LDS per workgroup cost the third resident workgroup; K chunks
+// of half the length (KCHUNK 128, WKCHUNK 64): 1603 / 825 us per launch, 14.38 ms per step. Three stages and these chunk lengths stay.)
 template <class CFG> struct GroupStages { static constexpr int n = 3; };
 template <> struct GroupStages<W256> { static constexpr int n = 2; };
 

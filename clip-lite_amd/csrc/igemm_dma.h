@@ -147,6 +147,17 @@ template <int ROWBYTES> DEV int xc_seg_xor(int k) {
   return ROWBYTES == 128 ? ((k >> 1) & 1) : (k & 3);      // 128 B rows: 2 k-rows per 256-B bank row; >= 256 B rows: one or less
 }
 
+// One LDS-DMA instruction of an XC loader. UNTRACKED = the assembly form that the compiler does not model (intrin.h): for kernels whose fragment
+// reads are transposed reads, behind which the compiler otherwise drains the ring (gemm_group.hip). The wave-simulator build has one form only.
+template <bool UNTRACKED> DEV void xc_dma16(rsrc_t r, uint32_t off, void* lds_wave_base) {
+#ifdef CLITE_WAVESIM_H
+  buf_load16_lds(r, off, lds_wave_base);
+#else
+  if constexpr (UNTRACKED) buf_load16_lds_untracked(r, off, lds_wave_base);
+  else buf_load16_lds(r, off, lds_wave_base);
+#endif
+}
+
 // ---- XC strided (weights in dgrad, dY in wgrad, linear weights in input-grad): element (k, x) at ptr[(k0+krow)*ld + rs*Cx + x]
 template <typename T, int COLS, int BK, int NW = 4>           // NW: waves per workgroup that share the tile's DMA instructions
 struct DmaXCStrided {
@@ -189,12 +200,13 @@ struct DmaXCStrided {
     st.k0 = kk - st.rs * Ck;
     locate(st);
   }
+  template <bool UNTRACKED = false>
   DEV void issue(State& st, char* lds, int wave, int, int) const {
     const uint32_t step = (uint32_t)(BK * ld) * (uint32_t)sizeof(T);
 #pragma unroll
     for (int j = 0; j < NI; ++j) {
       bool v = st.x[j] >= 0 && st.k0 + st.krow[j] < Ck && st.rs < RS;
-      buf_load16_lds(st.rs_, v ? st.off[j] : OOB_OFF, lds + (wave * NI + j) * 1024);
+      xc_dma16<UNTRACKED>(st.rs_, v ? st.off[j] : OOB_OFF, lds + (wave * NI + j) * 1024);
       st.off[j] += step;
     }
     st.k0 += BK;
@@ -259,6 +271,7 @@ struct DmaXCGather {
     }
     st.p0 = t_begin * BK;
   }
+  template <bool UNTRACKED = false>
   DEV void issue(State& st, char* lds, int wave, int, int) const {
 #pragma unroll
     for (int j = 0; j < NI; ++j) {
@@ -272,7 +285,7 @@ struct DmaXCGather {
       int wi = (int)wo * g.stride - g.padw + st.s[j];
       v = v && (unsigned)hi < (unsigned)g.H && (unsigned)wi < (unsigned)g.W;
       uint32_t off = v ? (uint32_t)((int)n * g.sN + hi * g.sH + wi * g.sW + st.xoff[j]) * (uint32_t)sizeof(T) : OOB_OFF;
-      buf_load16_lds(st.rs_, off, lds + (wave * NI + j) * 1024);
+      xc_dma16<UNTRACKED>(st.rs_, off, lds + (wave * NI + j) * 1024);
     }
     st.p0 += BK;
   }

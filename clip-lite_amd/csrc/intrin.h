@@ -53,6 +53,18 @@ DEV void buf_load16_lds(rsrc_t r, uint32_t off, void* lds_wave_base) {
 DEV void buf_load16_lds_nt(rsrc_t r, uint32_t off, void* lds_wave_base) {
   __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds_wave_base, 16, off, 0, 0, 2);
 }
+// The same instruction as one assembly statement, which the compiler neither counts on vmcnt nor models as an LDS write. The builtin form is an
+// LDS write of unknown extent to the compiler: it drains vmcnt(0) in front of the first ds_read_b64_tr_* that follows it (it cannot tell that the
+// read is of another ring stage), which serialises a K tile's DMA with its fragment reads. With this form the ONLY ordering between the DMA and
+// the LDS reads is the kernel's own wait_vmcnt<N>() + barrier_raw(); N counts these loads by hand. M0 (the wave-uniform LDS destination) is
+// written in the statement that reads it; `s_nop 3` covers M0 -> LDS-DMA (1 state) and a descriptor SGPR fresh from a VALU write (5 with the s_mov).
+#pragma clang diagnostic push
+#pragma clang diagnostic ignored "-Winline-asm"          // "clobber list contains reserved registers: m0" — the clobber is the point
+DEV void buf_load16_lds_untracked(rsrc_t r, uint32_t off, void* lds_wave_base) {
+  const uint32_t dst = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) void*)lds_wave_base;
+  asm volatile("s_mov_b32 m0, %0\n\ts_nop 3\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(dst), "v"(off), "s"(r) : "memory", "m0");
+}
+#pragma clang diagnostic pop
 template <int N> DEV void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 // Makes a value opaque to the optimiser at this point (no instruction): everything derived from it afterwards is computed where it is used
 // instead of being hoisted out of an enclosing loop into dozens of live registers.
