@@ -162,6 +162,9 @@ class Config(object):
         _C.OPTIM.LOOKAHEAD.USE = True
         _C.OPTIM.LOOKAHEAD.ALPHA = 0.5
         _C.OPTIM.LOOKAHEAD.STEPS = 5
+        _C.OPTIM.LARS = Node()          # OPTIMIZER_NAME "lars": SGD (SGD_MOMENTUM) with per-tensor trust ratios (optim.FusedLARS)
+        _C.OPTIM.LARS.TRUST_COEFFICIENT = 0.001
+        _C.OPTIM.LARS.EPS = 1e-8
         _C.OPTIM.BATCH_SIZE = 256
         _C.OPTIM.CNN_LR = 0.2
         _C.OPTIM.LR = 0.001

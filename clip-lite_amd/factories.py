@@ -13,7 +13,7 @@ from .config import Config
 from .encoder import ImageEncoder, TextEncoder
 from .loss import InfoNCELoss, JSDInfoMaxLoss
 from .model import VLInfoModel
-from .optim import FusedAdamW, FusedSGD, Lookahead, lr_scheduler
+from .optim import FusedAdamW, FusedLARS, FusedSGD, Lookahead, lr_scheduler
 
 
 class Factory(object):
@@ -186,7 +186,7 @@ class PretrainingModelFactory(Factory):
 
 
 class OptimizerFactory(Factory):
-    PRODUCTS: Dict[str, Callable] = {"sgd": FusedSGD, "adamw": FusedAdamW}
+    PRODUCTS: Dict[str, Callable] = {"sgd": FusedSGD, "adamw": FusedAdamW, "lars": FusedLARS}
 
     @classmethod
     def from_config(cls, config: Config, named_parameters: Iterable[Any]):
@@ -201,7 +201,9 @@ class OptimizerFactory(Factory):
             else:
                 lr = _C.OPTIM.LR
             param_groups.append({"params": [param], "lr": lr, "weight_decay": wd})
-        kwargs = {"momentum": _C.OPTIM.SGD_MOMENTUM} if _C.OPTIM.OPTIMIZER_NAME == "sgd" else {}          # (reference factories.py:478-483)
+        kwargs = {"momentum": _C.OPTIM.SGD_MOMENTUM} if _C.OPTIM.OPTIMIZER_NAME in ("sgd", "lars") else {}          # (reference factories.py:478-483)
+        if _C.OPTIM.OPTIMIZER_NAME == "lars":
+            kwargs.update(trust_coefficient=_C.OPTIM.LARS.TRUST_COEFFICIENT, eps=_C.OPTIM.LARS.EPS)
         optimizer = cls.create(_C.OPTIM.OPTIMIZER_NAME, param_groups, **kwargs)
         if _C.OPTIM.LOOKAHEAD.USE:
             optimizer = Lookahead(optimizer, k=_C.OPTIM.LOOKAHEAD.STEPS, alpha=_C.OPTIM.LOOKAHEAD.ALPHA)

@@ -188,6 +188,8 @@ _SIGNATURES = {
     "clite_sgd_step": [_V, _V, _V, _V, _V, _V, _I, _V, _V, _V],
     "clite_adamw_step": [_V, _V, _V, _V, _V, _V, _V, _I, _V, _V, _V],
     "clite_cast_bf16": [_V, _V, _U64, _V],
+    "clite_lars_norms": [_V, _V, _V, _I, _V, _V, _I, _V],
+    "clite_lars_step": [_V, _V, _V, _V, _V, _V, _I, _V, _V, _V, _I, _V],
 }
 
 _lib = None
@@ -1027,6 +1029,18 @@ def sum_slices(src, slices, stride, n, dst):
 
 def sgd_step(pf, gf, vf, slow, cast, items_ptr, n_items, hp, ss):
     check(lib().clite_sgd_step(p(pf), p(gf), p(vf), p(slow), p(cast), items_ptr, n_items, p(hp), p(ss), stream_ptr(pf)), "sgd_step")
+
+
+def lars_norms(pf, gf, items_ptr, n_items, partials, norms):
+    """norms [slots][2] = (sum p^2, sum g^2) of the adapted tensors of the launched items; partials: f32, two per launched item."""
+    if partials.numel() < 2 * n_items:
+        raise RuntimeError("lars_norms: partials holds fewer than two floats per item")
+    check(lib().clite_lars_norms(p(pf), p(gf), items_ptr, n_items, p(partials), p(norms), norms.numel() // 2, stream_ptr(pf)), "lars_norms")
+
+
+def lars_step(pf, gf, vf, slow, cast, items_ptr, n_items, hp, ss, norms):
+    check(lib().clite_lars_step(p(pf), p(gf), p(vf), p(slow), p(cast), items_ptr, n_items, p(hp), p(ss), p(norms), norms.numel() // 2,
+                                stream_ptr(pf)), "lars_step")
 
 
 def adamw_step(pf, gf, mf, v2f, slow, cast, items_ptr, n_items, hp, ss):

@@ -210,6 +210,87 @@ class FusedSGD(torch.optim.Optimizer):
         self._items_key = None
 
 
+class FusedLARS(FusedSGD):
+    """LARS (You, Gitman, Ginsburg 2017; the update SimCLR-style recipes run at batch sizes of 1k .. 32k) on FusedSGD's arena, work items, clipping,
+    Lookahead hook, captured-step protocol and checkpoint layout (torch SGD's `momentum_buffer`, which is what LARS wrappers around torch.optim.SGD
+    save): for every trainable tensor of two or more dimensions the SGD gradient term g' + wd p is scaled by the trust ratio
+    trust_coefficient |p| / (|g'| + wd |p| + eps), where g' is the pre-scaled, clipped gradient (1 where either norm is zero); biases and
+    normalisation scales (ndim <= 1) move exactly as under FusedSGD. The per-tensor norms are two launches over the item table
+    (clite_lars_norms: fixed order, no float atomics), the update one (clite_lars_step); launch(span) takes the norms of the span it updates."""
+
+    def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0, trust_coefficient=0.001, eps=1e-8):
+        super().__init__(params, lr=lr, momentum=momentum, weight_decay=weight_decay)
+        self.trust_coefficient, self.eps = float(trust_coefficient), float(eps)
+        plist = [p for g in self.param_groups for p in g["params"]]
+        adapted = [p for p in plist if p.dim() >= 2]
+        self._slots = {id(p): i for i, p in enumerate(adapted)}
+        self._spans = {self.arena.index[p._clite[1]][0]: self.arena.index[p._clite[1]][1] for p in adapted}      # arena offset -> elements
+        dev = self.arena.device
+        self.norms = torch.zeros(max(len(adapted), 1), 2, device=dev, dtype=torch.float32)      # (sum p^2, sum g^2) per adapted tensor
+        n_items = sum(((self.arena.index[p._clite[1]][1] + 3) // 4 * 4 + CHUNK - 1) // CHUNK for p in plist)
+        self.norm_partials = torch.zeros(2 * max(n_items, 1), device=dev, dtype=torch.float32)  # clite_lars_norms' first stage: a pair per item
+
+    def _build_items(self):
+        """FusedSGD's table, then the `reserved` word of every item of an adapted tensor: that tensor's norm slot + 1."""
+        if self._base_lrs() == self._items_key:
+            return
+        super()._build_items()
+        import bisect
+        owners = sorted((self.arena.index[p._clite[1]][0], self._slots[id(p)] + 1) for g in self.param_groups for p in g["params"] if id(p) in self._slots)
+        offs = [o for o, _ in owners]
+        arr = (hip.OptimItem * self._n_items).from_buffer_copy(self._items.cpu().numpy().tobytes())
+        for i, start in enumerate(self._item_starts):          # items never straddle tensors: the owner is the last tensor starting at or before the item
+            k = bisect.bisect_right(offs, start) - 1
+            if k >= 0 and start < offs[k] + self._spans[owners[k][0]]:
+                arr[i].reserved = owners[k][1]
+        self._items = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.arena.device)
+
+    def upload_hp(self, lookahead_sync=False, alpha=1.0, max_norm=None):
+        """FusedSGD.upload_hp with the trust coefficient and eps in slots 6 and 7."""
+        mom = self.param_groups[0]["momentum"]
+        mn = self.max_norm if max_norm is None else float(max_norm)
+        vals = [self._lr_mult(), mom, mn, 1.0 if lookahead_sync else 0.0, alpha, self.grad_prescale, self.trust_coefficient, self.eps]
+        if not self.hp.is_cuda:
+            self.hp.copy_(torch.tensor(vals))
+            return
+        if self._hp_ring is None:
+            self._hp_ring = [(torch.empty(8, dtype=torch.float32).pin_memory(), torch.cuda.Event()) for _ in range(8)]
+            self._hp_used = [False] * 8
+            self._hp_next = 0
+        i = self._hp_next
+        self._hp_next = (i + 1) % len(self._hp_ring)
+        host, ev = self._hp_ring[i]
+        if self._hp_used[i]:
+            ev.synchronize()
+        host.copy_(torch.tensor(vals))
+        self.hp.copy_(host, non_blocking=True)
+        ev.record()
+        self._hp_used[i] = True
+
+    def tensor_norms(self, p):
+        """(|p|, |g|) of an adapted parameter as the last launch that updated it measured them (raw gradient: before pre-scale and clipping)."""
+        return tuple(self.norms[self._slots[id(p)]].double().sqrt().tolist())
+
+    @torch.no_grad()
+    def launch(self, span=None):
+        self.arena.join()
+        self._build_items()
+        self.zero_frozen()
+        first, n = 0, self._n_items
+        if span is not None:
+            import bisect
+            first = bisect.bisect_left(self._item_starts, span[0])
+            n = bisect.bisect_left(self._item_starts, span[1]) - first
+        if n > 0:
+            items = C.c_void_p(self._items.data_ptr() + first * C.sizeof(hip.OptimItem))
+            # every span has its own share of the partials: two spans may be in flight on two streams (TrainStep: update_img / update_rest)
+            hip.lars_norms(self.arena.flat_p, self.arena.flat_g, items, n, self.norm_partials[2 * first:2 * (first + n)], self.norms)
+            hip.lars_step(self.arena.flat_p, self.arena.flat_g, self.flat_v, self.flat_slow, self.arena.flat_lp, items, n, self.hp, self.sumsq,
+                          self.norms)
+        self.arena._tr_stale = True
+        self._dirty = False
+
+
 class FusedAdamW(FusedSGD):
     """torch.optim.AdamW (reference factories.py:439, `OPTIM.OPTIMIZER_NAME: adamw`, torch's default betas / eps) on the same arena, work items, clipping,
     Lookahead hook and captured-step protocol as FusedSGD (clite_adamw_step). `state_dict()` keeps torch.optim.AdamW's layout (step, exp_avg, exp_avg_sq

@@ -758,7 +758,7 @@ typedef struct clite_optim_item {   /* one workgroup's slice of one parameter te
   uint32_t count;                   /* elements, multiple of 4 */
   float lr;                         /* base learning rate of the owning tensor's param group */
   float wd;                         /* weight decay of the owning tensor's param group */
-  uint32_t reserved;
+  uint32_t reserved;                /* clite_lars_*: slot of the owning tensor in `norms` + 1; 0 = not adapted (LARS). The other kernels ignore it. */
 } clite_optim_item;
 /* out (f32 scalar, pre-zeroed) += sum x^2 — the global gradient norm of clip_grad_norm_. Two fixed-order stages through `partials`
  * (device f32[n_partials], n_partials >= 1; 1024 slots use the whole chip): no float atomics, so the value is a pure function of x and every
@@ -780,6 +780,25 @@ int clite_sgd_step(float* p, float* g, float* v, float* slow, void* cast_bf16, c
 int clite_adamw_step(float* p, float* g, float* m, float* v2, float* slow, void* cast_bf16, const clite_optim_item* items, int n_items,
                      const float* hp, const float* sumsq, void* stream);
 int clite_cast_bf16(const float* src, void* dst, uint64_t n, void* stream);
+/* LARS (You, Gitman, Ginsburg 2017: layer-wise adaptive rate scaling; the update SimCLR-style recipes run at batch sizes of 1k .. 32k) on the
+ * same item table: SGD whose step for every ADAPTED tensor is scaled by a trust ratio. An item's `reserved` word holds the owning tensor's slot
+ * + 1 (0: not adapted — biases, normalisation scales); a tensor's items are contiguous in the table and in arena order.
+ *
+ * clite_lars_norms: norms[2 slot] = sum p^2, norms[2 slot + 1] = sum g^2 over the raw p and g of every adapted tensor whose items lie in the
+ * launched table (a tensor is launched whole or not at all); slots of other tensors are untouched. Two fixed-order stages, no float atomics:
+ * every item's workgroup stores its pair into partials[2 i], partials[2 i + 1] (i: index in the launched table; device f32[2 n_items]), then
+ * the workgroup of a tensor's FIRST item folds that tensor's pairs in item order. The result is a pure function of the data (bit-identical
+ * between runs and between data-parallel ranks) and does not depend on which other tensors share the launch. Items whose reserved word
+ * exceeds n_slots are treated as not adapted by both entry points.
+ *
+ * clite_lars_step: clite_sgd_step with, per adapted tensor, pn = sqrt(norms[2 slot]), gn = prescale clip sqrt(norms[2 slot + 1]),
+ * q = eta pn / (gn + wd pn + eps) if pn > 0 and gn > 0, else 1 (q = 1 for items that are not adapted, which never read norms):
+ * u = q (g prescale clip + wd p); v = mu v + u; p -= lr mult v; then the Lookahead sync, the zeroing of g and the bf16 copy as there.
+ * hp (device f32[8]): as clite_sgd_step, with [6] = eta (trust coefficient), [7] = eps. With every q = 1 the result is clite_sgd_step's bit for bit. */
+int clite_lars_norms(const float* p, const float* g, const clite_optim_item* items, int n_items, float* partials, float* norms, int n_slots,
+                     void* stream);
+int clite_lars_step(float* p, float* g, float* v, float* slow, void* cast_bf16, const clite_optim_item* items, int n_items, const float* hp,
+                    const float* sumsq, const float* norms, int n_slots, void* stream);
 
 #ifdef __cplusplus
 }
