@@ -11,34 +11,24 @@
 // reduces with wave shuffles; a workgroup owns CLITE_LOGREG_ROWS rows of one problem. They stream [N][P * Cp] once and are HBM-bound; the GEMMs
 // carry the FLOPs. Every sum is formed in one fixed order (shuffle butterflies, LDS trees, partials in block order), no float
 // atomics: reruns are bit-identical whatever the deterministic switch says.
-#include "vec.h"
-#include "clite.h"
+#include "newton_cg.h"
 
 using namespace clite;
 
 namespace {
 
+using ncg::block_sum_d;
+
+// the line search's columns, after the shared ones (ncg::G0 ... ncg::DPHI0, newton_cg.h)
 enum {
-  L_G0 = 0, L_GN, L_REL, L_RR, L_CGTOL2, L_STEP, L_NEWTON, L_CGIT, L_CGTOT, L_ACTIVE, L_CGACT, L_CGLAST, L_DPHI0,
-  L_T, L_LO, L_HI, L_WD, L_DD, L_LSDONE, L_SPARE0, L_SPARE1, L_EVALS
+  L_T = ncg::NCG_COLS, L_LO, L_HI, L_WD, L_DD, L_LSDONE, L_SPARE0, L_SPARE1, L_EVALS
 };
+static_assert(L_T == 13, "include/clite.h documents the columns by number");
 static_assert(L_EVALS < CLITE_LOGREG_STATE, "state table too narrow");
 
-constexpr int NT = 256;                       // threads of every workgroup here
+constexpr int NT = ncg::NT;                   // threads of every workgroup here
 constexpr int ROWS = CLITE_LOGREG_ROWS;       // rows per workgroup of the row kernels
 constexpr float LS_TOL = 1e-4f;               // the line search stops at |phi'(t)| <= LS_TOL |phi'(0)|
-
-// sum over the 256 threads of a workgroup as a fixed LDS tree in double; every thread gets the result
-DEV double block_sum_d(double v, double* red) {
-  __syncthreads();
-  red[threadIdx.x] = v;
-  __syncthreads();
-  for (int s = NT / 2; s > 0; s >>= 1) {
-    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-    __syncthreads();
-  }
-  return red[0];
-}
 
 // column of element e of chunk u of this lane
 DEV int col_of(int u, int lane) { return (u * 64 + lane) * 4; }
@@ -225,101 +215,11 @@ __global__ __launch_bounds__(NT) void logreg_ray_kernel(const float* Z, const fl
   }
 }
 
-// One workgroup per problem: the gradient norm, the stopping test and, for a problem that goes on, a fresh CG solve of H x = -g (x = 0,
-// r = d = -g, CG tolerance (eta |g|)^2 with eta = min(eta_max, sqrt(|g| / |g0|))). |g0| is |grad f(0)|: recorded by a g0_only call at W = 0, or
-// by the first call when none was made (a cold start, where W = 0).
-__global__ __launch_bounds__(NT) void logreg_newton_begin_kernel(const float* G, int ld, int n, float* X, float* R, float* D, float* st, float tol,
-                                                                 int max_newton, float eta_max, int g0_only) {
-  __shared__ double red[NT];
-  __shared__ int go;
-  const int p = blockIdx.x;
-  float* s = st + (size_t)p * CLITE_LOGREG_STATE;
-  const float* g = G + (size_t)p * ld;
-  double a = 0.0;
-  for (int k = threadIdx.x; k < n; k += NT) a += (double)g[k] * (double)g[k];
-  const double gn2 = block_sum_d(a, red);
-  if (threadIdx.x == 0) {
-    const float gn = (float)sqrt(gn2);
-    int act = 0;
-    if (g0_only) {
-      s[L_G0] = gn;
-    } else {
-      act = s[L_ACTIVE] != 0.f;
-      if (act) {
-        if (s[L_NEWTON] == 0.f && s[L_G0] == 0.f) s[L_G0] = gn;
-        const float g0 = s[L_G0];
-        const float rel = g0 > 0.f ? gn / g0 : 0.f;
-        s[L_GN] = gn;
-        s[L_REL] = rel;
-        // a line search that ended at step 0 left W where it was: the next iteration would repeat this one, so the problem stops short of tol
-        if (rel <= tol || s[L_NEWTON] >= (float)max_newton || (s[L_NEWTON] > 0.f && s[L_STEP] == 0.f)) act = 0;
-        if (act) {
-          const float eta = fminf(eta_max, sqrtf(rel));
-          s[L_NEWTON] += 1.f;
-          s[L_RR] = (float)gn2;
-          s[L_CGTOL2] = (eta * gn) * (eta * gn);
-          s[L_CGLAST] = s[L_CGIT];
-          s[L_CGIT] = 0.f;
-        }
-        s[L_ACTIVE] = act ? 1.f : 0.f;
-      }
-      s[L_CGACT] = act ? 1.f : 0.f;
-    }
-    go = act;
-  }
-  __syncthreads();
-  if (!go) return;
-  float* x = X + (size_t)p * ld;
-  float* r = R + (size_t)p * ld;
-  float* d = D + (size_t)p * ld;
-  for (int k = threadIdx.x; k < n; k += NT) {
-    x[k] = 0.f;
-    r[k] = -g[k];
-    d[k] = -g[k];
-  }
-}
-
-// One CG iteration per problem still solving: alpha = r.r / d.Hd, x += alpha d, r -= alpha Hd, then stop (|r|^2 <= tol) or d = r + beta d.
-__global__ __launch_bounds__(NT) void logreg_cg_update_kernel(const float* HD, int ld, int n, float* X, float* R, float* D, float* st) {
-  __shared__ double red[NT];
-  const int p = blockIdx.x;
-  float* s = st + (size_t)p * CLITE_LOGREG_STATE;
-  if (s[L_CGACT] == 0.f) return;                 // uniform over the workgroup; only this workgroup writes s
-  const float rr = s[L_RR], tol2 = s[L_CGTOL2];
-  const float* hd = HD + (size_t)p * ld;
-  float* x = X + (size_t)p * ld;
-  float* r = R + (size_t)p * ld;
-  float* d = D + (size_t)p * ld;
-  double a = 0.0;
-  for (int k = threadIdx.x; k < n; k += NT) a += (double)d[k] * (double)hd[k];
-  const float dhd = (float)block_sum_d(a, red);
-  if (!(dhd > 0.f) || !(rr > 0.f)) {             // H >= I: only a zero direction gets here
-    __syncthreads();
-    if (threadIdx.x == 0) s[L_CGACT] = 0.f;
-    return;
-  }
-  const float alpha = rr / dhd;
-  a = 0.0;
-  for (int k = threadIdx.x; k < n; k += NT) {
-    x[k] += alpha * d[k];
-    const float rk = r[k] - alpha * hd[k];
-    r[k] = rk;
-    a += (double)rk * (double)rk;
-  }
-  const float rn = (float)block_sum_d(a, red);
-  const bool stop = rn <= tol2;
-  if (!stop) {
-    const float beta = rn / rr;
-    for (int k = threadIdx.x; k < n; k += NT) d[k] = r[k] + beta * d[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    s[L_CGIT] += 1.f;
-    s[L_CGTOT] += 1.f;
-    if (stop) s[L_CGACT] = 0.f;
-    else s[L_RR] = rn;
-  }
-}
+// newton_begin and cg_update are the shared Newton-CG kernels (newton_cg.h) over a problem's span of n = Cp * Dp floats, with the dots in
+// double through the LDS tree, and with the rule set a warm start needs: |g0| = |grad f(0)| is recorded by a g0_only call at W = 0, or by the
+// first call when none was made (a cold start, where W = 0), and a problem whose line search ended at step 0 is frozen.
+constexpr auto logreg_newton_begin_kernel = ncg::newton_begin_kernel<ncg::DoubleTree, CLITE_LOGREG_STATE, ncg::Rules::RecordedG0>;
+constexpr auto logreg_cg_update_kernel = ncg::cg_update_kernel<ncg::DoubleTree, CLITE_LOGREG_STATE>;
 
 // Start of the line search along D for one problem per workgroup: phi'(0) = <G, D>, <W, D>, |D|^2; t = 1, bracket [0, inf). A problem that is
 // not active, or whose D is no descent direction, is done at t = 0.
@@ -341,15 +241,15 @@ __global__ __launch_bounds__(NT) void logreg_ray_begin_kernel(const float* G, co
   wd = block_sum_d(wd, red);
   dd = block_sum_d(dd, red);
   if (threadIdx.x == 0) {
-    const bool go = s[L_ACTIVE] != 0.f && (float)gd < 0.f && (float)dd > 0.f;
-    s[L_DPHI0] = (float)gd;
+    const bool go = s[ncg::ACTIVE] != 0.f && (float)gd < 0.f && (float)dd > 0.f;
+    s[ncg::DPHI0] = (float)gd;
     s[L_WD] = (float)wd;
     s[L_DD] = (float)dd;
     s[L_T] = go ? 1.f : 0.f;
     s[L_LO] = 0.f;
     s[L_HI] = INFINITY;
     s[L_EVALS] = 0.f;
-    s[L_STEP] = 0.f;
+    s[ncg::STEP] = 0.f;
     s[L_LSDONE] = go ? 0.f : 1.f;
   }
 }
@@ -374,20 +274,16 @@ __global__ __launch_bounds__(NT) void logreg_ray_step_kernel(const float* part1,
       const float g = (float)((double)s[L_WD] + (double)t * (double)s[L_DD] + a);      // phi'(t)
       const float h = (float)((double)s[L_DD] + b);                                   // phi''(t) >= |D|^2 > 0
       s[L_EVALS] += 1.f;
-      if (fabsf(g) <= LS_TOL * fabsf(s[L_DPHI0])) {
-        s[L_STEP] = t;
+      if (fabsf(g) <= LS_TOL * fabsf(s[ncg::DPHI0])) {
+        s[ncg::STEP] = t;
         s[L_LSDONE] = 1.f;
       } else {
-        if (g < 0.f) s[L_LO] = t;
-        else s[L_HI] = t;
-        const float lo = s[L_LO], hi = s[L_HI];
-        float tn = t - g / h;
-        if (!(tn > lo && tn < hi)) tn = hi < INFINITY ? 0.5f * (lo + hi) : 2.f * t;
+        const float tn = ncg::bracket_newton_step(t, g, h, s[L_LO], s[L_HI]);
         if (tn == t) {
-          s[L_STEP] = t;
+          s[ncg::STEP] = t;
           s[L_LSDONE] = 1.f;
         } else if (last) {                       // out of evaluations: the bracket's left end. phi' < 0 on [0, lo], so phi(lo) <= phi(0); a point
-          s[L_STEP] = lo;                        // right of the minimiser has no such guarantee, so with no left end found the step is 0
+          s[ncg::STEP] = s[L_LO];                // right of the minimiser has no such guarantee, so with no left end found the step is 0
           s[L_LSDONE] = 1.f;
         } else {
           s[L_T] = tn;
@@ -402,7 +298,7 @@ __global__ __launch_bounds__(NT) void logreg_ray_step_kernel(const float* part1,
 __global__ __launch_bounds__(NT) void logreg_ray_finish_kernel(float* W, const float* D, int ld, int n, const float* st) {
   const int p = blockIdx.y;
   const float* s = st + (size_t)p * CLITE_LOGREG_STATE;
-  const float t = s[L_LSDONE] != 0.f ? s[L_STEP] : 0.f;
+  const float t = s[L_LSDONE] != 0.f ? s[ncg::STEP] : 0.f;
   if (t == 0.f) return;
   float* w = W + (size_t)p * ld;
   const float* d = D + (size_t)p * ld;

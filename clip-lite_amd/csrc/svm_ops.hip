@@ -9,34 +9,20 @@
 // reproducible whatever the deterministic switch says. Column kernels give a workgroup SVM_CB adjacent problems and split its rows over
 // 256 / SVM_CB row groups: a wave reads 64 / SVM_CB rows of SVM_CB * 4 contiguous bytes. Everything is memory- or latency-bound; the GEMMs
 // carry the FLOPs.
-#include "vec.h"
-#include "clite.h"
+#include "newton_cg.h"
 
 using namespace clite;
 
 namespace {
 
-enum {
-  S_G0 = 0, S_GN, S_REL, S_RR, S_CGTOL2, S_STEP, S_NEWTON, S_CGIT, S_CGTOT, S_ACTIVE, S_CGACT, S_CGLAST, S_DPHI0
-};
-static_assert(S_DPHI0 < CLITE_SVM_STATE, "state table too narrow");
+static_assert(ncg::DPHI0 < CLITE_SVM_STATE, "state table too narrow");      // the state columns are ncg:: (newton_cg.h), nothing added
 
-constexpr int NT = 256;                   // threads of every workgroup here
+constexpr int NT = ncg::NT;               // threads of every workgroup here
 constexpr int SVM_CB = 8;                 // problems per workgroup of the column kernels
 constexpr int SVM_RG = NT / SVM_CB;       // row groups
 constexpr int MARGIN_ROWS = 512;          // rows per workgroup of the margin kernel (grid.y = ceil(N / 512))
 constexpr int LS_MAX = 24;                // line-search iterations (safeguarded Newton on a piecewise quadratic; usually 2-4)
 constexpr int AP_MAX = CLITE_SVM_AP_MAX_ROWS;
-
-// sum over the 256 threads of a workgroup in a fixed order; every thread gets the result
-DEV float block_sum(float v, float* red) {
-  v = wave_sum(v);
-  const int w = threadIdx.x >> 6;
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[w] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // S = c 1_I (z - y), H = c 1_I with I = {y z < 1}; part[blockIdx.y][p] = sum over this block's rows of c max(0, 1 - y z)^2.
 // Columns p in [P, ldp) are written as zeros (they feed the GEMMs).
@@ -98,94 +84,10 @@ __global__ __launch_bounds__(NT) void svm_hess_scale_kernel(const float* H, floa
   }
 }
 
-// One workgroup per problem: the gradient norm, the stopping test and, for a problem that goes on, a fresh CG solve of H x = -g
-// (x = 0, r = d = -g, CG tolerance (eta ||g||)^2 with eta = min(eta_max, sqrt(||g|| / ||g0||))).
-__global__ __launch_bounds__(NT) void svm_newton_begin_kernel(const float* G, int ld, int Dp, float* X, float* R, float* D, float* st, float tol,
-                                                              int max_newton, float eta_max) {
-  __shared__ float red[4];
-  __shared__ int go;
-  const int p = blockIdx.x;
-  float* s = st + (size_t)p * CLITE_SVM_STATE;
-  const float* g = G + (size_t)p * ld;
-  float a = 0.f;
-  for (int k = threadIdx.x; k < Dp; k += NT) a += g[k] * g[k];
-  const float gn2 = block_sum(a, red);
-  if (threadIdx.x == 0) {
-    const float gn = sqrtf(gn2);
-    int act = s[S_ACTIVE] != 0.f;
-    if (act) {
-      if (s[S_NEWTON] == 0.f) s[S_G0] = gn;      // w = 0 before the first step: this is ||grad f(0)||
-      const float g0 = s[S_G0];
-      const float rel = g0 > 0.f ? gn / g0 : 0.f;
-      s[S_GN] = gn;
-      s[S_REL] = rel;
-      if (rel <= tol || s[S_NEWTON] >= (float)max_newton) act = 0;
-      if (act) {
-        const float eta = fminf(eta_max, sqrtf(rel));
-        s[S_NEWTON] += 1.f;
-        s[S_RR] = gn2;
-        s[S_CGTOL2] = (eta * gn) * (eta * gn);
-        s[S_CGLAST] = s[S_CGIT];
-        s[S_CGIT] = 0.f;
-      }
-      s[S_ACTIVE] = act ? 1.f : 0.f;
-    }
-    s[S_CGACT] = act ? 1.f : 0.f;
-    go = act;
-  }
-  __syncthreads();
-  if (!go) return;
-  float* x = X + (size_t)p * ld;
-  float* r = R + (size_t)p * ld;
-  float* d = D + (size_t)p * ld;
-  for (int k = threadIdx.x; k < Dp; k += NT) {
-    x[k] = 0.f;
-    r[k] = -g[k];
-    d[k] = -g[k];
-  }
-}
-
-// One CG iteration per problem still solving: alpha = r.r / d.Hd, x += alpha d, r -= alpha Hd, then stop (||r||^2 <= tol) or d = r + beta d.
-__global__ __launch_bounds__(NT) void svm_cg_update_kernel(const float* HD, int ld, int Dp, float* X, float* R, float* D, float* st) {
-  __shared__ float red[4];
-  const int p = blockIdx.x;
-  float* s = st + (size_t)p * CLITE_SVM_STATE;
-  if (s[S_CGACT] == 0.f) return;                 // uniform over the workgroup; only this workgroup writes s
-  const float rr = s[S_RR], tol2 = s[S_CGTOL2];
-  const float* hd = HD + (size_t)p * ld;
-  float* x = X + (size_t)p * ld;
-  float* r = R + (size_t)p * ld;
-  float* d = D + (size_t)p * ld;
-  float a = 0.f;
-  for (int k = threadIdx.x; k < Dp; k += NT) a += d[k] * hd[k];
-  const float dhd = block_sum(a, red);
-  if (!(dhd > 0.f) || !(rr > 0.f)) {             // H >= I: only a zero direction gets here
-    __syncthreads();
-    if (threadIdx.x == 0) s[S_CGACT] = 0.f;
-    return;
-  }
-  const float alpha = rr / dhd;
-  a = 0.f;
-  for (int k = threadIdx.x; k < Dp; k += NT) {
-    x[k] += alpha * d[k];
-    const float rk = r[k] - alpha * hd[k];
-    r[k] = rk;
-    a += rk * rk;
-  }
-  const float rn = block_sum(a, red);
-  const bool stop = rn <= tol2;
-  if (!stop) {
-    const float beta = rn / rr;
-    for (int k = threadIdx.x; k < Dp; k += NT) d[k] = r[k] + beta * d[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    s[S_CGIT] += 1.f;
-    s[S_CGTOT] += 1.f;
-    if (stop) s[S_CGACT] = 0.f;
-    else s[S_RR] = rn;
-  }
-}
+// newton_begin and cg_update are the shared Newton-CG kernels (newton_cg.h) with float sums over 4 floats of LDS, and with the rule set in which
+// g0 is the first gradient seen and a zero step does not freeze a problem.
+constexpr auto svm_newton_begin_kernel = ncg::newton_begin_kernel<ncg::FloatSum, CLITE_SVM_STATE, ncg::Rules::FirstGradient>;
+constexpr auto svm_cg_update_kernel = ncg::cg_update_kernel<ncg::FloatSum, CLITE_SVM_STATE>;
 
 // Step length along the Newton direction x for SVM_CB problems per workgroup: the minimiser of the convex piecewise quadratic
 //   phi(t) = 1/2 |w + t x|^2 + sum_i c_i max(0, 1 - y_i (z_i + t delta_i))^2,   delta = X~ x,
@@ -221,7 +123,7 @@ __global__ __launch_bounds__(NT) void svm_line_search_kernel(const float* Z, con
       }
       sh_wx[threadIdx.x] = a;
       sh_xx[threadIdx.x] = b;
-      const bool act = pp < P && st[(size_t)pp * CLITE_SVM_STATE + S_ACTIVE] != 0.f;
+      const bool act = pp < P && st[(size_t)pp * CLITE_SVM_STATE + ncg::ACTIVE] != 0.f;
       sh_t[threadIdx.x] = 0.f;                   // the first pass evaluates phi'(0) = g.x
       sh_lo[threadIdx.x] = 0.f;
       sh_hi[threadIdx.x] = INFINITY;
@@ -280,13 +182,9 @@ __global__ __launch_bounds__(NT) void svm_line_search_kernel(const float* Z, con
       } else if (fabsf(g) <= 1e-6f * fabsf(sh_d0[q])) {
         sh_done[q] = 1;
       } else {
-        if (g < 0.f) sh_lo[q] = tq;
-        else sh_hi[q] = tq;
-        float tn = tq - g / h;
-        const float lo = sh_lo[q], hi = sh_hi[q];
-        if (!(tn > lo && tn < hi)) tn = hi < INFINITY ? 0.5f * (lo + hi) : 2.f * tq;
+        const float tn = ncg::bracket_newton_step(tq, g, h, sh_lo[q], sh_hi[q]);
         if (tn == tq) sh_done[q] = 1;
-        else if (it == LS_MAX) sh_t[q] = lo;       // out of iterations: the last point known to lie left of the minimiser
+        else if (it == LS_MAX) sh_t[q] = sh_lo[q];   // out of iterations: the last point known to lie left of the minimiser
         else sh_t[q] = tn;
       }
     }
@@ -304,15 +202,15 @@ __global__ __launch_bounds__(NT) void svm_line_search_kernel(const float* Z, con
     const int pp = p0 + q;
     if (pp >= P) break;
     float* s = st + (size_t)pp * CLITE_SVM_STATE;
-    if (s[S_ACTIVE] == 0.f) continue;
+    if (s[ncg::ACTIVE] == 0.f) continue;
     const float t = sh_t[q];
     float* w = W + (size_t)pp * ld;
     const float* x = X + (size_t)pp * ld;
     if (t != 0.f)
       for (int k = threadIdx.x; k < Dp; k += NT) w[k] += t * x[k];
     if (threadIdx.x == 0) {
-      s[S_STEP] = t;
-      s[S_DPHI0] = sh_d0[q];
+      s[ncg::STEP] = t;
+      s[ncg::DPHI0] = sh_d0[q];
     }
   }
 }
@@ -437,7 +335,8 @@ extern "C" int clite_svm_hess_scale(const float* H, float* Q, uint64_t n, void* 
 extern "C" int clite_svm_newton_begin(const float* G, int ld, int Dp, int P, float* X, float* R, float* D, float* state, float tol,
                                       int max_newton, float eta_max, void* stream) {
   if (!G || !X || !R || !D || !state || P <= 0 || Dp <= 0 || ld < Dp || max_newton < 0 || !(eta_max > 0.f)) return -1;
-  hipLaunchKernelGGL(svm_newton_begin_kernel, dim3(P), dim3(NT), 0, (hipStream_t)stream, G, ld, Dp, X, R, D, state, tol, max_newton, eta_max);
+  hipLaunchKernelGGL(svm_newton_begin_kernel, dim3(P), dim3(NT), 0, (hipStream_t)stream, G, ld, Dp, X, R, D, state, tol, max_newton, eta_max,
+                     0);      // g0_only: not read under Rules::FirstGradient
   return (int)hipGetLastError();
 }
 

@@ -945,6 +945,9 @@ def xent_bwd(dt, logits, ld, B, Bp, C, lse, labels, acc, gout, dlogits, ldd):
 
 SVM_STATE = 16                 # include/clite.h CLITE_SVM_STATE: per-problem scalars of the batched SVM solver
 SVM_AP_MAX_ROWS = 8192         # include/clite.h CLITE_SVM_AP_MAX_ROWS
+# The columns the host reads of a Newton-CG state table, SVM_STATE or LOGREG_STATE wide: the enum of csrc/newton_cg.h, where all 13 shared
+# columns are named (newton_cg.solve, svm.fit_squared_hinge and logreg.fit use these).
+NCG_G0, NCG_GN, NCG_REL, NCG_NEWTON, NCG_CGTOT, NCG_ACTIVE, NCG_CGLAST = 0, 1, 2, 6, 8, 9, 11
 
 
 def svm_margin(Z, Y, Cw, N, P, ldp, S, H, loss, work):
@@ -1115,7 +1118,7 @@ def knn_vote(top_s, top_i, labels, Q, K, N, Cn, ks, inv_T, class_scores, pred):
 
 
 # ------------------------------------------------------------------------------------------------ logistic-regression probe (clip_lite_amd/logreg.py)
-LOGREG_STATE, LOGREG_ROWS, LOGREG_MAX_CLASSES = 24, 32, 4096              # include/clite.h CLITE_LOGREG_*
+LOGREG_STATE, LOGREG_ROWS, LOGREG_MAX_CLASSES = 24, 32, 4096              # include/clite.h CLITE_LOGREG_*; state columns: NCG_* above
 
 
 def logreg_blocks(N):

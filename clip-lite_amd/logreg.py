@@ -15,18 +15,13 @@ from typing import Dict, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import hip
-from .svm import augment
+from . import hip, newton_cg
+from .svm import _ceil8, augment
 from .utils.common import logger
 
-_S_REL, _S_NEWTON, _S_CGTOT, _S_ACTIVE, _S_CGLAST = 2, 6, 8, 9, 11        # include/clite.h: columns of the state table
 DEFAULT_COSTS = (1.0, 10.0, 100.0, 1000.0)
 _ROW_OPERANDS = 3                                   # Z, Pr and one scratch shared by S, Q and delta
 _LS_EVALS = 8                                       # line-search evaluations enqueued per Newton iteration (a finished search skips the rest)
-
-
-def _ceil8(n: int) -> int:
-    return (n + 7) // 8 * 8
 
 
 def _check_shape(name: str, x) -> None:
@@ -142,35 +137,28 @@ def _solve_group(Xt, y32, costs, w, C, W, tol, max_newton, max_cg, eta_max, warm
     loss = torch.zeros(P, device=dev, dtype=torch.float32)
     work = torch.zeros(2 * hip.logreg_blocks(N) * P, device=dev, dtype=torch.float32)
     state = torch.zeros(P, hip.LOGREG_STATE, device=dev, dtype=torch.float32)
-    state[:, _S_ACTIVE] = 1.0
+    state[:, hip.NCG_ACTIVE] = 1.0
 
     def grad(Wc):
         _nt(Xt, Wc, N, ldz, Dp, Z)                                      # z = X~ W^T
         hip.logreg_softmax(Z, y32, costs, w, N, P, C, ldz, Pr, T, loss, work)
         _tn(T, Xt, ldz, Dp, N, G, Wc)                                   # g = W + S^T X~
 
+    def hess_vec():
+        _nt(Xt, Dc, N, ldz, Dp, T)                                      # q = X~ d^T
+        hip.logreg_hess_apply(Pr, costs, w, N, P, C, ldz, T)
+        _tn(T, Xt, ldz, Dp, N, HD, Dc)                                  # Hd = d + Q^T X~
+
+    def line_search():
+        _nt(Xt, Xd, N, ldz, Dp, T)                                      # delta = X~ x^T
+        hip.logreg_line_search(Z, T, y32, costs, w, N, P, C, ldz, G, W, Xd, n, n, state, work, _LS_EVALS)
+
     if warm:                                                            # |grad f(0)| of the stopping rule, which a warm start does not pass through
         grad(HD)                                                        # HD is still zero
         hip.logreg_newton_begin(G, n, n, P, Xd, R, Dc, state, tol, max_newton, eta_max, g0_only=True)
-    cap, launched = min(max_cg, 10), 0                                  # the first solve runs at eta = 0.1: ten iterations, or a descent direction anyway
-    for _ in range(max_newton + 1):
-        grad(W)
-        hip.logreg_newton_begin(G, n, n, P, Xd, R, Dc, state, tol, max_newton, eta_max)
-        st = state.cpu()                                                # the one read-back of this Newton iteration
-        active = st[:, _S_ACTIVE] != 0
-        if not bool(active.any()):
-            break
-        if launched:
-            used = int(st[active, _S_CGLAST].max().item())
-            cap = min(max_cg, max(10, 2 * used))
-        for _ in range(cap):
-            _nt(Xt, Dc, N, ldz, Dp, T)                                  # q = X~ d^T
-            hip.logreg_hess_apply(Pr, costs, w, N, P, C, ldz, T)
-            _tn(T, Xt, ldz, Dp, N, HD, Dc)                              # Hd = d + Q^T X~
-            hip.logreg_cg_update(HD, n, n, P, Xd, R, Dc, state)
-        launched += cap
-        _nt(Xt, Xd, N, ldz, Dp, T)                                      # delta = X~ x^T
-        hip.logreg_line_search(Z, T, y32, costs, w, N, P, C, ldz, G, W, Xd, n, n, state, work, _LS_EVALS)
+    launched = newton_cg.solve(state, lambda: hip.logreg_newton_begin(G, n, n, P, Xd, R, Dc, state, tol, max_newton, eta_max),
+                               lambda: hip.logreg_cg_update(HD, n, n, P, Xd, R, Dc, state), lambda: grad(W), hess_vec, line_search,
+                               max_newton, max_cg, first_cap=min(max_cg, 10))      # eta = 0.1 in the first solve: ten iterations, or a descent direction anyway
     return state.cpu(), loss.cpu(), launched
 
 
@@ -229,9 +217,9 @@ def fit(X: torch.Tensor, y, num_classes: int, costs: Sequence[float], weights=No
             Wg = Wall[p0:p0 + g].reshape(g * Cp, Dp)                    # a view: the group's result lands in Wall
             st, ls, la = _solve_group(Xt, y32, cd[p0:p0 + g].contiguous(), wd[:, p0:p0 + g].contiguous(), num_classes, Wg, float(tol),
                                       int(max_newton), int(max_cg), float(eta_max), W0 is not None)
-            newton[p0:p0 + g] = st[:, _S_NEWTON].to(torch.int64)
-            cg[p0:p0 + g] = st[:, _S_CGTOT].to(torch.int64)
-            rel[p0:p0 + g] = st[:, _S_REL]
+            newton[p0:p0 + g] = st[:, hip.NCG_NEWTON].to(torch.int64)
+            cg[p0:p0 + g] = st[:, hip.NCG_CGTOT].to(torch.int64)
+            rel[p0:p0 + g] = st[:, hip.NCG_REL]
             loss[p0:p0 + g] = ls
             launched += la
     finally:

@@ -13,9 +13,8 @@ from typing import Dict, Sequence
 import numpy as np
 import torch
 
-from . import hip
+from . import hip, newton_cg
 
-_S_G0, _S_GN, _S_REL, _S_NEWTON, _S_CGTOT, _S_ACTIVE, _S_CGLAST = 0, 1, 2, 6, 8, 9, 11
 SVM_COSTS = (0.01, 0.1, 1.0, 10.0)                  # reference voc_clf.py:83
 CLASS_WEIGHT = {1: 2.0, -1: 1.0}                    # reference voc_clf.py:97 class_weight={1: 2, -1: 1}
 
@@ -75,31 +74,28 @@ def fit_squared_hinge(X: torch.Tensor, Y: torch.Tensor, Cw: torch.Tensor, tol: f
     loss = torch.zeros(P, device=dev, dtype=torch.float32)
     work = torch.zeros((N + 511) // 512, ldp, device=dev, dtype=torch.float32)
     state = torch.zeros(P, hip.SVM_STATE, device=dev, dtype=torch.float32)
-    state[:, _S_ACTIVE] = 1.0
-    cap, launched = max_cg, 0
-    for _ in range(max_newton + 1):
+    state[:, hip.NCG_ACTIVE] = 1.0
+
+    def grad():
         _nt(Xt, W, N, ldp, Dp, Z)                                   # z = X~ w
         hip.svm_margin(Z, Yp, Cp, N, P, ldp, S, H, loss, work)
         _tn(S, Xt, ldp, Dp, N, G, W)                                # g = w + 2 X~^T (c 1_I (z - y))
-        hip.svm_newton_begin(G, Dp, Dp, P, Xd, R, Dc, state, tol, max_newton, eta_max)
-        st = state.cpu()                                            # the one read-back of this Newton iteration
-        active = st[:, _S_ACTIVE] != 0
-        if not bool(active.any()):
-            break
-        if launched:
-            used = int(st[active, _S_CGLAST].max().item())
-            cap = min(max_cg, max(10, 2 * used))
-        for _ in range(cap):
-            _nt(Xt, Dc, N, ldp, Dp, Q)                              # q = X~ d
-            hip.svm_hess_scale(H, Q)                                # q *= c 1_I
-            _tn(Q, Xt, ldp, Dp, N, HD, Dc)                          # Hd = d + 2 X~^T q
-            hip.svm_cg_update(HD, Dp, Dp, P, Xd, R, Dc, state)
-        launched += cap
+
+    def hess_vec():
+        _nt(Xt, Dc, N, ldp, Dp, Q)                                  # q = X~ d
+        hip.svm_hess_scale(H, Q)                                    # q *= c 1_I
+        _tn(Q, Xt, ldp, Dp, N, HD, Dc)                              # Hd = d + 2 X~^T q
+
+    def line_search():
         _nt(Xt, Xd, N, ldp, Dp, Q)                                  # delta = X~ x
         hip.svm_line_search(Z, Q, Yp, Cp, N, P, ldp, W, Xd, Dp, Dp, state)
+
+    launched = newton_cg.solve(state, lambda: hip.svm_newton_begin(G, Dp, Dp, P, Xd, R, Dc, state, tol, max_newton, eta_max),
+                               lambda: hip.svm_cg_update(HD, Dp, Dp, P, Xd, R, Dc, state), grad, hess_vec, line_search,
+                               max_newton, max_cg, first_cap=max_cg)
     st = state.cpu()
-    return {"W": W[:P, :D].clone(), "b": W[:P, D].clone(), "newton": st[:, _S_NEWTON].to(torch.int64),
-            "rel_grad": st[:, _S_REL].clone(), "cg": st[:, _S_CGTOT].to(torch.int64), "cg_launched": launched}
+    return {"W": W[:P, :D].clone(), "b": W[:P, D].clone(), "newton": st[:, hip.NCG_NEWTON].to(torch.int64),
+            "rel_grad": st[:, hip.NCG_REL].clone(), "cg": st[:, hip.NCG_CGTOT].to(torch.int64), "cg_launched": launched}
 
 
 @torch.no_grad()
