@@ -677,6 +677,57 @@ class VOC07ClassificationDataset(Dataset):
     collate_fn = staticmethod(_label_collate)
 
 
+def read_gender_records(path: str):
+    """The reference's COCO gender annotation `<split>.data` (bias_eda.py's GenderDataset source): a pickled list of dicts with `image_id`,
+    `file_name` and a one-hot `gender` ([1, 0] man, [0, 1] woman). Returns [(image_id, file name inside <split>2017/, group)] with group 0 =
+    men, 1 = women, in file order; a record without exactly one of the two set is refused."""
+    import pickle
+    with open(path, "rb") as fh:
+        records = pickle.load(fh)
+    if not isinstance(records, (list, tuple)) or not records:
+        raise ValueError(f"{path}: expected a pickled non-empty list of records")
+    out = []
+    for i, r in enumerate(records):
+        try:
+            g = [int(v) for v in r["gender"]]
+            name, image_id = str(r["file_name"]).split("_")[-1], int(r["image_id"])
+        except (KeyError, TypeError, ValueError) as e:
+            raise ValueError(f"{path}: record {i} needs image_id, file_name and gender ({e!r})")
+        if g not in ([1, 0], [0, 1]):
+            raise ValueError(f"{path}: record {i} has gender {g}; expected [1, 0] (man) or [0, 1] (woman)")
+        out.append((image_id, name, g[1]))
+    return out
+
+
+class GenderAnnotationDataset(Dataset):
+    """COCO images with the reference's gender annotation (reference bias_eda.py): records from <gender_data_path>/<split>.data
+    (read_gender_records), images at <data_root>/<split>2017/<file_name.split("_")[-1]>. The groups are `classes` = ["men", "women"].
+    Items as ImageFolderDataset's: {"image": f32 [3][H][W], "label": the group}."""
+    classes = ["men", "women"]
+
+    def __init__(self, data_root: str, gender_data_path: str, split: str = "train", image_transform=DEFAULT_IMAGE_TRANSFORM,
+                 image_size: int = 224, seed: int = 0):
+        records = read_gender_records(os.path.join(gender_data_path, f"{split}.data"))
+        self.image_ids = [r[0] for r in records]
+        self.samples = [(os.path.join(data_root, f"{split}2017", r[1]), r[2]) for r in records]
+        self.targets = [t for _, t in self.samples]
+        self.image_transform, self.image_size, self.seed = tuple(image_transform), image_size, seed
+
+    @property
+    def num_classes(self):
+        return len(self.classes)
+
+    def __len__(self):
+        return len(self.samples)
+
+    def __getitem__(self, idx):
+        path, label = self.samples[idx]
+        g = torch.Generator().manual_seed(self.seed * 1000003 + idx)
+        return {"image": load_image(path, self.image_transform, self.image_size, g), "label": torch.tensor(label, dtype=torch.long)}
+
+    collate_fn = staticmethod(_label_collate)
+
+
 # ------------------------------------------------------------------------------------------------ image-text retrieval
 def pre_caption(caption: str, max_words: int = 30) -> str:
     """The reference's retrieval caption cleanup (data/dataloader.py:1027-1052): lower-case; delete , . ' ! ? " ( ) * # : ; ~; '-' and '/'

@@ -1,6 +1,6 @@
 """Command lines of the downstream evaluations: `linear_clf.py` (linear probe / fine-tune, reference linear_clf.py:25-300) and `zero_shot.py`
 (reference zero_shot.py), on ImageClassifier / zero_shot_counts (classify.py); `voc_clf.py` (svm.py), `knn_clf.py` (knn.py), `logreg_clf.py`
-(logreg.py) and `retrieval.py` (retrieval.py). One GPU: the reference's multi-GPU launch, hipGraph capture of the classification step, and the `clip` / `imagenet`
+(logreg.py), `retrieval.py` (retrieval.py) and `bias_eval.py` (debias.py). One GPU: the reference's multi-GPU launch, hipGraph capture of the classification step, and the `clip` / `imagenet`
 initialisations (the `clip` package, torchvision downloads) are not available."""
 import argparse
 import os
@@ -683,3 +683,161 @@ def cluster_main(_A):
 
 def cluster_cli(argv=None):
     return cluster_main(build_cluster_parser().parse_args(argv))
+
+
+# ------------------------------------------------------------------------------------------------ bias evaluation
+# Bolukbasi et al. 2016, "Man is to computer programmer as woman is to homemaker?": the ten definitional pairs (the reference's
+# definitional_pairs.json)
+DEFINITIONAL_PAIRS = (("woman", "man"), ("girl", "boy"), ("she", "he"), ("mother", "father"), ("daughter", "son"), ("gal", "guy"),
+                      ("female", "male"), ("her", "his"), ("herself", "himself"), ("mary", "john"))
+
+
+def build_bias_eval_parser():
+    parser = common_parser(description="Bias evaluation of a pretrained model: a direction found in the text embeddings of definitional word "
+                                       "pairs is removed from the image features; what a prompt retrieves from every group of images is "
+                                       "compared before and after (reference bias_eda.py, without its prompt loop).")
+    parser.set_defaults(num_gpus_per_machine=1)
+    group = parser.add_argument_group("Downstream config arguments.")
+    group.add_argument("--down-config", metavar="FILE", help="Path to a downstream config file.")
+    group.add_argument("--down-config-override", nargs="*", default=[], help="A list of key-value pairs to modify downstream config params.")
+    group = parser.add_argument_group("Checkpointing")
+    group.add_argument("--weight-init", choices=["random", "imagenet", "torchvision", "vlinfo", "clip"], default="vlinfo",
+                       help="'vlinfo': the pretraining checkpoint --checkpoint-path; 'random': the randomly initialised model. 'imagenet', "
+                            "'torchvision' (downloads) and 'clip' (the clip package) are not supported.")
+    group.add_argument("--checkpoint-path", default=None, help="Pretraining checkpoint to evaluate.")
+    group = parser.add_argument_group("Evaluation")
+    group.add_argument("--split", default="train", help="Which data split to use (reference: train, val or test).")
+    group.add_argument("--gender-data-path", metavar="DIR", default=None, help="The reference's COCO gender annotation: DIR/<split>.data, a "
+                       "pickled list of {image_id, file_name, gender}; images under <DATA.ROOT>/<split>2017/. Without it DATA.ROOT is an "
+                       "image folder root/<split>/<group>/<image>, or 'random'.")
+    group.add_argument("--pairs", metavar="FILE", default=None, help="JSON list of two-string lists (the reference's definitional_pairs.json); "
+                                                                     "default: Bolukbasi's ten gender pairs.")
+    group.add_argument("--query", nargs="+", default=[], metavar="TEXT", help="Prompt(s) to retrieve with.")
+    group.add_argument("--queries", metavar="FILE", default=None, help="File with one prompt per line.")
+    group.add_argument("--num-results", type=int, default=10, help="Images retrieved per prompt and group.")
+    group.add_argument("--components", type=int, default=1, help="Principal directions to remove.")
+    group.add_argument("--max-length", type=int, default=30, help="Token length of pair words and prompts (padded); at most 128 with the BERT "
+                                                                  "tower, 32 with MPNet.")
+    group.add_argument("--output", metavar="FILE", default=None, help="Write the result dict as JSON.")
+    return parser
+
+
+def read_pairs(path):
+    """[(a, b)] from a JSON list of two-string lists (the reference's definitional_pairs.json)."""
+    import json
+    with open(path) as fh:
+        pairs = json.load(fh)
+    if not isinstance(pairs, list) or not pairs or any(not isinstance(p, (list, tuple)) or len(p) != 2 or not all(isinstance(w, str) and w.strip() for w in p)
+                                                       for p in pairs):
+        raise SystemExit(f"bias_eval: {path} must hold a non-empty JSON list of two-string lists, e.g. [[\"woman\", \"man\"], ...]")
+    return [(p[0], p[1]) for p in pairs]
+
+
+def read_queries(path):
+    """The non-empty lines of a prompt file."""
+    with open(path) as fh:
+        return [line.strip() for line in fh if line.strip()]
+
+
+def _check_bias_eval_launch(_A):
+    """(pairs, prompts) after every refusal that needs no config."""
+    if _A.weight_init == "clip":
+        raise SystemExit("bias_eval: --weight-init clip needs the clip package, which is not part of the reference; use vlinfo or random")
+    if _A.weight_init in ("imagenet", "torchvision"):
+        raise SystemExit(f"bias_eval: --weight-init {_A.weight_init} needs torchvision model-zoo downloads, which are not supported here; use "
+                         "vlinfo or random")
+    if _A.weight_init == "vlinfo" and not _A.checkpoint_path:
+        raise SystemExit("bias_eval: --weight-init vlinfo needs --checkpoint-path (or pass --weight-init random)")
+    if _A.num_gpus_per_machine > 1 or _A.num_machines > 1:
+        raise SystemExit("bias_eval: runs on one GPU (--num-gpus-per-machine 1)")
+    if _A.num_gpus_per_machine == 0:
+        raise SystemExit("bias_eval: the encoders and the debias kernels run on the MI355X only; there is no CPU path (--num-gpus-per-machine 1)")
+    from . import hip
+    pairs = read_pairs(_A.pairs) if _A.pairs else list(DEFINITIONAL_PAIRS)
+    prompts = list(_A.query) + (read_queries(_A.queries) if _A.queries else [])
+    if not prompts:
+        raise SystemExit("bias_eval: at least one prompt is required (--query TEXT ... or --queries FILE)")
+    if len(pairs) > hip.DEBIAS_MAX_PAIRS:
+        raise SystemExit(f"bias_eval: at most {hip.DEBIAS_MAX_PAIRS} pairs, got {len(pairs)}")
+    if not 1 <= _A.components <= min(len(pairs), hip.DEBIAS_MAX_COMPONENTS):
+        raise SystemExit(f"bias_eval: --components must be in [1, {min(len(pairs), hip.DEBIAS_MAX_COMPONENTS)}] for {len(pairs)} pairs, got "
+                         f"{_A.components}")
+    if not 1 <= _A.num_results <= hip.KNN_MAX_K:
+        raise SystemExit(f"bias_eval: --num-results must be in [1, {hip.KNN_MAX_K}], got {_A.num_results}")
+    return pairs, prompts
+
+
+def _check_bias_eval_model(_A, _C):
+    from .data import text_framing
+    if _C.MODEL.LOSS.TYPE not in ("dot", "dotcon"):
+        raise SystemExit(f"bias_eval: MODEL.LOSS.TYPE {_C.MODEL.LOSS.TYPE} has no projection heads (loss.global_d.img_block / text_block), which "
+                         "carry both towers into the space the direction lives in; the reference's --loss-type concat path never worked either")
+    limit = 128 if text_framing(_C.MODEL.TEXTUAL.NETWORK_NAME) == "bert" else 32
+    if not 1 <= _A.max_length <= limit:
+        raise SystemExit(f"bias_eval: --max-length {_A.max_length} exceeds the {limit} tokens of the text tower {_C.MODEL.TEXTUAL.NETWORK_NAME}")
+
+
+def report_bias(res, prompts, group_names):
+    """The per-prompt lines bias_eval prints: mean alignment and share of every group, before and after."""
+    lines = []
+    for q, text in enumerate(prompts):
+        lines.append(f"prompt {text!r}")
+        for g, name in enumerate(group_names):
+            ma, sh = res["mean_alignment"], res["share"]
+            lines.append(f"  Mean Alignment | {name} | Biased: {ma['biased'][q][g]:.6f} | Debiased: {ma['debiased'][q][g]:.6f} || share of the top "
+                         f"{res['k']}: {sh['biased'][q][g]:.3f} -> {sh['debiased'][q][g]:.3f} (prior {res['group_sizes'][g] / res['num_images']:.3f})")
+    return lines
+
+
+def bias_eval_main(_A):
+    """Reference bias_eda.py as an evaluation: unnormalised projected text embeddings of the definitional pairs -> principal directions
+    (debias.directions); unnormalised projected image features of the split with their groups; normalised prompt embeddings;
+    debias.evaluate. Prints the per-prompt report and the result dict (also written to --output as JSON) and returns the dict."""
+    import json
+    import numpy as np
+    pairs, prompts = _check_bias_eval_launch(_A)
+    _DOWNC = Config(_A.down_config, _A.down_config_override)
+    _C = Config(_A.config, list(_A.config_override) + ["AMP", _DOWNC.AMP])       # the compute dtype follows the downstream config
+    _check_bias_eval_model(_A, _C)
+    if not torch.cuda.is_available():
+        raise SystemExit("bias_eval: no GPU visible; the encoders and the debias kernels run on the MI355X only")
+    from . import debias, retrieval
+    device = torch.device("cuda", torch.cuda.current_device())
+    common_setup(_DOWNC, _A, job_type="downstream")
+    synthetic = _DOWNC.DATA.ROOT == "random" and not _A.gender_data_path
+    dataset = DownstreamDatasetFactory.from_config(_DOWNC, split=_A.split, gender_data_path=_A.gender_data_path, num_classes=2 if synthetic else None)
+    groups = [dataset.label(i) for i in range(len(dataset))] if synthetic else list(dataset.targets)
+    g, G = debias.check_groups(np.asarray(groups, dtype=np.int64), len(dataset), _A.num_results)
+    loader = DataLoader(dataset, batch_size=_DOWNC.OPTIM.BATCH_SIZE, shuffle=False, num_workers=_A.cpu_workers, pin_memory=True,
+                        collate_fn=dataset.collate_fn)
+    arch = PretrainingModelFactory.from_config(_C)
+    if _A.weight_init == "vlinfo":
+        CheckpointManager(model=arch).load(_A.checkpoint_path)
+    arch = arch.to(device)
+    vocab, text_model = _C.DATA.TOKENIZER_VOCAB, _C.MODEL.TEXTUAL.NETWORK_NAME
+    sides = []
+    for side in (0, 1):
+        ids, mask = tokenize_texts([p[side] for p in pairs], _A.max_length, vocab, text_model)
+        sides.append(retrieval.embed_texts(arch, ids.to(device), mask.to(device), normalize=False))
+    comps, evr = debias.directions(sides[0], sides[1], _A.components)
+    ids, mask = tokenize_texts(prompts, _A.max_length, vocab, text_model)
+    prompt_embeds = retrieval.embed_texts(arch, ids.to(device), mask.to(device))
+    feats, labels = [], []
+    for batch in loader:
+        feats.append(retrieval.embed_images(arch, batch["image"].to(device, non_blocking=True), normalize=False).float())
+        labels.append(batch["label"].reshape(-1))
+    if not np.array_equal(torch.cat(labels).numpy(), g):
+        raise ValueError("bias_eval: the loader's labels differ from the dataset's groups")
+    res = debias.evaluate(torch.cat(feats, 0), g, prompt_embeds, comps, _A.num_results, evr.tolist())
+    res.update({"prompts": prompts, "groups": [str(c) for c in dataset.classes], "pairs": [list(p) for p in pairs]})
+    for line in report_bias(res, prompts, res["groups"]):
+        print(line)
+    print(json.dumps(res))
+    if _A.output:
+        with open(_A.output, "w") as fh:
+            json.dump(res, fh)
+    return res
+
+
+def bias_eval_cli(argv=None):
+    return bias_eval_main(build_bias_eval_parser().parse_args(argv))

@@ -77,9 +77,10 @@ class DownstreamDatasetFactory(Factory):
     is the synthetic RandomLabelledDataset; a VOC2007 root (the last path component contains "voc") with split "trainval" or "test" is
     VOC07ClassificationDataset, the source of voc_clf.py's SVM evaluation; any other root is an image folder root/{train,val}/<class>/<image>
     (ImageFolderDataset, the layout of the reference's ImageNetDataset / INaturalist2018Dataset). A VOC root with another split (linear_clf.py's
-    train / val) and VOC detection (voc_det.py: detectron2) are not supported."""
+    train / val) and VOC detection (voc_det.py: detectron2) are not supported. bias_eval.py passes `gender_data_path` (the reference's COCO
+    gender annotation over a COCO root: GenderAnnotationDataset) or `num_classes` (the number of groups of the synthetic source)."""
     PRODUCTS: Dict[str, Callable] = {"random": vdata.RandomLabelledDataset, "folder": vdata.ImageFolderDataset,
-                                     "voc": vdata.VOC07ClassificationDataset}
+                                     "voc": vdata.VOC07ClassificationDataset, "gender": vdata.GenderAnnotationDataset}
     # reference linear_clf.py:105 (the dataset name is the last path component of DATA.ROOT; "imagenet2012" means "imagenet")
     NUM_CLASSES_MAPPING = {"imagenet": 1000, "inaturalist": 8142}
 
@@ -89,9 +90,14 @@ class DownstreamDatasetFactory(Factory):
         return "imagenet" if name == "imagenet2012" else name
 
     @classmethod
-    def from_config(cls, config: Config, split: str = "train"):
+    def from_config(cls, config: Config, split: str = "train", gender_data_path: str = None, num_classes: int = None):
         _C = config
         root = _C.DATA.ROOT
+        if gender_data_path:
+            if root == "random":
+                raise ValueError("the gender annotation needs the COCO images: set DATA.ROOT to the COCO root (<root>/<split>2017/<image>)")
+            return cls.create("gender", data_root=root, gender_data_path=gender_data_path, split=split,
+                              image_transform=tuple(_C.DATA.IMAGE_TRANSFORM_VAL), image_size=_C.DATA.IMAGE_CROP_SIZE, seed=_C.RANDOM_SEED)
         if "voc" in cls.dataset_name(root).lower():
             if split not in ("trainval", "test"):
                 raise NotImplementedError(f"VOC2007 split {split!r}: VOC2007 is evaluated by voc_clf.py's SVMs on 'trainval' / 'test'; "
@@ -100,8 +106,9 @@ class DownstreamDatasetFactory(Factory):
             return cls.create("voc", data_root=root, split=split, image_transform=transform, image_size=_C.DATA.IMAGE_CROP_SIZE,
                               seed=_C.RANDOM_SEED)
         if root == "random":
+            extra = {} if num_classes is None else {"num_classes": int(num_classes)}
             return cls.create("random", image_size=_C.DATA.IMAGE_CROP_SIZE, length=50000 if split == "train" else 500, split=split,
-                              seed=_C.RANDOM_SEED)
+                              seed=_C.RANDOM_SEED, **extra)
         transform = tuple(_C.DATA.IMAGE_TRANSFORM_TRAIN if "train" in split else _C.DATA.IMAGE_TRANSFORM_VAL)
         ds = cls.create("folder", data_root=root, split=split, image_transform=transform, image_size=_C.DATA.IMAGE_CROP_SIZE,
                         percentage=_C.DATA.USE_PERCENTAGE, seed=_C.RANDOM_SEED)

@@ -190,6 +190,8 @@ _SIGNATURES = {
     "clite_cast_bf16": [_V, _V, _U64, _V],
     "clite_lars_norms": [_V, _V, _V, _I, _V, _V, _I, _V],
     "clite_lars_step": [_V, _V, _V, _V, _V, _V, _I, _V, _V, _V, _I, _V],
+    "clite_debias_pca": [_V, _I, _I, _I, _V, _V, _V, _V, _V],
+    "clite_debias_rows": [_V, _V, _I, _I, _I, _V, _V, _V, _V],
 }
 
 _lib = None
@@ -1115,6 +1117,29 @@ def knn_vote(top_s, top_i, labels, Q, K, N, Cn, ks, inv_T, class_scores, pred):
     ks_host = (C.c_int32 * nk)(*ks)
     check(lib().clite_knn_vote(p(top_s), p(top_i), p(labels), Q, K, N, Cn, C.cast(ks_host, C.c_void_p), nk, float(inv_T), p(class_scores), p(pred),
                                stream_ptr(top_s)), "knn_vote")
+
+
+# ------------------------------------------------------------------------------------------------ bias evaluation (clip_lite_amd/debias.py)
+DEBIAS_MAX_PAIRS, DEBIAS_MAX_COMPONENTS, DEBIAS_MAX_DIM = 64, 8, 4096     # include/clite.h CLITE_DEBIAS_*
+
+
+def debias_pca(diffs, P, D, R, eigvals, components, work, info):
+    """eigvals [P] (descending) and components [R][D] of the pair differences diffs [P][D]; info int32 [2] = (error code, sweeps), left on
+    the device (include/clite.h: clite_debias_pca)."""
+    assert all(t.dtype == torch.float32 and t.is_contiguous() for t in (diffs, eigvals, components, work)) and info.dtype == torch.int32
+    assert 1 <= P <= DEBIAS_MAX_PAIRS and 0 < D <= DEBIAS_MAX_DIM and D % 8 == 0 and 1 <= R <= min(P, DEBIAS_MAX_COMPONENTS)
+    assert diffs.numel() >= P * D and eigvals.numel() >= P and components.numel() >= R * D and work.numel() >= P * P and info.numel() >= 2
+    check(lib().clite_debias_pca(p(diffs), P, D, R, p(eigvals), p(components), p(work), p(info), stream_ptr(diffs)), "debias_pca")
+
+
+def debias_rows(x, components, N, D, R, xn, xd, coef):
+    """xn = x / |x|, xd = the rows with the components projected out, normalised, coef = <x, v_j>; each may be None (include/clite.h:
+    clite_debias_rows)."""
+    assert all(t is None or (t.dtype == torch.float32 and t.is_contiguous()) for t in (x, components, xn, xd, coef))
+    assert N >= 1 and 0 < D <= DEBIAS_MAX_DIM and D % 8 == 0 and 1 <= R <= DEBIAS_MAX_COMPONENTS
+    assert x.numel() >= N * D and components.numel() >= R * D
+    assert (xn is None or xn.numel() >= N * D) and (xd is None or xd.numel() >= N * D) and (coef is None or coef.numel() >= N * R)
+    check(lib().clite_debias_rows(p(x), p(components), N, D, R, p(xn), p(xd), p(coef), stream_ptr(x)), "debias_rows")
 
 
 # ------------------------------------------------------------------------------------------------ logistic-regression probe (clip_lite_amd/logreg.py)

@@ -17,9 +17,10 @@ from . import hip
 
 
 @torch.no_grad()
-def embed_images(model, images: torch.Tensor, batch_size: int = 128) -> torch.Tensor:
+def embed_images(model, images: torch.Tensor, batch_size: int = 128, normalize: bool = True) -> torch.Tensor:
     """images: f32 NCHW on the model's device -> L2-normalised projected embeddings [N][2048] (compute dtype).
-    Reference retrieval.py:122-127: image_projector(image_encoder(image)) then F.normalize."""
+    Reference retrieval.py:122-127: image_projector(image_encoder(image)) then F.normalize. normalize=False returns the projected features
+    as they are (reference bias_eda.py drops the direction from the unnormalised features)."""
     rt = model.runtime
     enc, proj = model.image_encoder, model.loss.global_d.img_block
     was = (enc.training, proj.training)
@@ -27,17 +28,19 @@ def embed_images(model, images: torch.Tensor, batch_size: int = 128) -> torch.Te
     outs = []
     for i in range(0, images.shape[0], batch_size):
         f = proj(enc(images[i:i + batch_size]))
-        o = torch.empty_like(f)
-        hip.l2_normalize(rt.dt, f.contiguous(), o, f.shape[0], f.shape[1])
-        outs.append(o)
+        if normalize:
+            o = torch.empty_like(f)
+            hip.l2_normalize(rt.dt, f.contiguous(), o, f.shape[0], f.shape[1])
+            f = o
+        outs.append(f)
     enc.train(was[0]), proj.train(was[1])
     return torch.cat(outs, 0)
 
 
 @torch.no_grad()
-def embed_texts(model, input_ids: torch.Tensor, attention_mask: torch.Tensor, batch_size: int = 128) -> torch.Tensor:
+def embed_texts(model, input_ids: torch.Tensor, attention_mask: torch.Tensor, batch_size: int = 128, normalize: bool = True) -> torch.Tensor:
     """input_ids / attention_mask: int64 [N][L <= 128] (BERT; 32 for MPNet) -> L2-normalised projected embeddings [N][2048].
-    Reference retrieval.py:90-108: text_projector(text_encoder({...})) then F.normalize."""
+    Reference retrieval.py:90-108: text_projector(text_encoder({...})) then F.normalize. normalize=False: the projected features as they are."""
     rt = model.runtime
     enc, proj = model.text_encoder, model.loss.global_d.text_block
     was = (enc.training, proj.training)
@@ -45,9 +48,11 @@ def embed_texts(model, input_ids: torch.Tensor, attention_mask: torch.Tensor, ba
     outs = []
     for i in range(0, input_ids.shape[0], batch_size):
         f = proj(enc({"input_ids": input_ids[i:i + batch_size], "attention_mask": attention_mask[i:i + batch_size]}))
-        o = torch.empty_like(f)
-        hip.l2_normalize(rt.dt, f.contiguous(), o, f.shape[0], f.shape[1])
-        outs.append(o)
+        if normalize:
+            o = torch.empty_like(f)
+            hip.l2_normalize(rt.dt, f.contiguous(), o, f.shape[0], f.shape[1])
+            f = o
+        outs.append(f)
     enc.train(was[0]), proj.train(was[1])
     return torch.cat(outs, 0)
 

@@ -800,6 +800,31 @@ int clite_lars_norms(const float* p, const float* g, const clite_optim_item* ite
 int clite_lars_step(float* p, float* g, float* v, float* slow, void* cast_bf16, const clite_optim_item* items, int n_items, const float* hp,
                     const float* sumsq, const float* norms, int n_slots, void* stream);
 
+/* ---- Bias evaluation: a direction found in the text embedding space, removed from image features (reference bias_eda.py, utils/we.py;
+ * clip-lite_amd/debias.py). Additive to ABI v12. No float atomics: every result below is a pure function of its inputs, bit for bit. */
+#define CLITE_DEBIAS_MAX_PAIRS 64
+#define CLITE_DEBIAS_MAX_COMPONENTS 8
+#define CLITE_DEBIAS_MAX_DIM 4096
+/* The principal directions of the pair differences diffs, f32 [P][D] (row i = e(a_i) - e(b_i); 16-byte aligned): what we.doPCA's
+ * sklearn PCA of the 2 P rows +-d_i / 2 returns, whose column mean is zero, i.e. the right singular vectors of diffs. The P x P Gram matrix is
+ * formed in f32 with a fixed summation order (work: f32 [P * P]) and diagonalised in LDS by one workgroup (cyclic Jacobi, round-robin pairing,
+ * a bye for an odd P) until the off-diagonal norm is at most FLT_EPSILON x trace. eigvals: f32 [P], descending (the squared singular values
+ * of diffs; a rounding-negative one reads 0; not finite, and last, when the f32 Gram matrix overflowed). components: f32 [R][D] = normalised diffs^T u_j of the R largest, after one modified
+ * Gram-Schmidt pass (orthonormal rows to f32 rounding), each row signed so that its entry of largest magnitude (the lowest index among equal
+ * ones) is positive. A direction whose eigenvalue is below ~P FLT_EPSILON eigvals[0] is rounding noise of the Gram matrix; the caller judges
+ * (debias.directions refuses below 1e-4). info: device int32 [2], written by the kernel like every other result (the call does not wait):
+ * info[0] = 0, or the error code 1 when 30 sweeps did not reach the bound (eigvals and components then hold the unconverged state);
+ * info[1] = sweeps run. Returns -1 and launches nothing for P outside [1, CLITE_DEBIAS_MAX_PAIRS], D not a positive multiple of 8 or above
+ * CLITE_DEBIAS_MAX_DIM, R outside [1, min(P, CLITE_DEBIAS_MAX_COMPONENTS)], a misaligned or a null pointer. */
+int clite_debias_pca(const float* diffs, int P, int D, int R, float* eigvals, float* components, float* work, int* info, void* stream);
+/* The streaming pass over x, f32 [N][D] (D as above; 16-byte aligned), with components f32 [R][D] (orthonormal rows; R in
+ * [1, CLITE_DEBIAS_MAX_COMPONENTS], held in LDS). Any of the outputs may be NULL:
+ *   coef [N][R] = <x, v_j>;   xn [N][D] = x / max(|x|, 1e-12);   xd [N][D] = y / max(|y|, 1e-12), y = x - sum_j <x, v_j> v_j
+ * (F.normalize's rule; |y| is the norm of y itself). One wave per row, the row in registers, 16-byte accesses; x is read once. With all three
+ * NULL nothing is launched (returns 0). Returns -1 and launches nothing for N < 1, a D or R outside the limits, a null x or components, or a
+ * misaligned x, components, xn or xd. */
+int clite_debias_rows(const float* x, const float* components, int N, int D, int R, float* xn, float* xd, float* coef, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
