@@ -71,6 +71,9 @@ class ImageClassifier(ResNet):
     Only ``fc`` learns (a linear probe). Otherwise the whole network is fine-tuned."""
 
     def __init__(self, visual_name: str = "resnet50", num_classes: int = 1000, frozen: bool = False, is_amp: bool = True):
+        if str(visual_name).startswith("vit_"):
+            raise ValueError(f"linear_clf: the classifier (linear probe / fine-tune) is built on a ResNet backbone; {visual_name!r} is a ViT image "
+                             "encoder: evaluate its features with logreg_clf.py or knn_clf.py instead")
         super().__init__(visual_name)
         if num_classes < 2:
             raise ValueError(f"num_classes must be >= 2, got {num_classes}")

@@ -1,5 +1,5 @@
 """Image and text encoders with the reference's call surface (reference encoder.py:13-65 ImageEncoder, :115-205 TextEncoder),
-running on the HIP executors in resnet.py / bert.py. Attribute names (`img_encoder`, `strans`, `fc1`/`fc2`) and state_dict keys
+running on the HIP executors in resnet.py / vit.py / bert.py. Attribute names (`img_encoder`, `strans`, `fc1`/`fc2`) and state_dict keys
 match the reference so checkpoints interchange."""
 from typing import Any, Dict
 
@@ -9,6 +9,7 @@ import torch.nn as nn
 from . import hip
 from .bert import BertModel, LinearParams, bert_backward, bert_forward
 from .resnet import ResNet, resnet_backward, resnet_forward
+from .vit import VisionTransformer, vit_backward, vit_forward
 
 
 def _runtime_of(module):
@@ -35,15 +36,35 @@ class _ResNetFn(torch.autograd.Function):
         return None, None, None, None, None
 
 
-class ImageEncoder(nn.Module):
-    r"""torchvision-topology ResNet with ``fc = Identity`` (reference encoder.py:28-65). ``pretrained`` weights cannot be
-    downloaded here (no network) and raise; ``frozen`` keeps all weights fixed and the encoder in eval mode."""
+class _ViTFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, image, anchor, enc, rt, training):
+        feat, saved = vit_forward(rt, enc.img_encoder, image.to(torch.float32).contiguous(), training)
+        ctx.enc, ctx.rt, ctx.saved = enc, rt, saved
+        return feat
 
-    def __init__(self, img_enc_net: str = "resnet50", pretrained: bool = False, frozen: bool = False):
+    @staticmethod
+    def backward(ctx, dfeat):
+        vit_backward(ctx.rt, ctx.enc.img_encoder, ctx.saved, dfeat.contiguous())
+        ctx.rt.arena.note_stream_work()
+        return None, None, None, None, None
+
+
+class ImageEncoder(nn.Module):
+    r"""torchvision-topology ResNet with ``fc = Identity`` (reference encoder.py:28-65), or — a name starting with ``vit_`` — torchvision's
+    ViT-B/32 / ViT-B/16 with ``heads = Identity`` (vit.py; built for ``image_size`` pixels, DATA.IMAGE_CROP_SIZE). ``pretrained`` weights cannot
+    be downloaded here (no network) and raise; ``frozen`` keeps all weights fixed and the encoder in eval mode."""
+
+    def __init__(self, img_enc_net: str = "resnet50", pretrained: bool = False, frozen: bool = False, image_size=224, **vit_kwargs):
+        """vit_kwargs: VisionTransformer's num_layers / hidden / heads / mlp_dim (small models for tests); a ResNet takes none."""
         super().__init__()
         if pretrained:
             raise RuntimeError("pretrained torchvision weights are not available offline; load a state_dict instead")
-        self.img_encoder = ResNet(img_enc_net)
+        self.is_vit = img_enc_net.startswith("vit_")
+        if vit_kwargs and not self.is_vit:
+            raise TypeError(f"ImageEncoder({img_enc_net!r}): unexpected arguments {sorted(vit_kwargs)}")
+        self.img_encoder = VisionTransformer(img_enc_net, image_size=image_size, **vit_kwargs) if self.is_vit else ResNet(img_enc_net)
+        self.out_dim = self.img_encoder.out_dim
         self.frozen = frozen
         if frozen:
             for param in self.img_encoder.parameters():
@@ -53,7 +74,13 @@ class ImageEncoder(nn.Module):
     def forward(self, image: torch.Tensor) -> torch.Tensor:
         rt = _runtime_of(self)
         training = self.img_encoder.training and not self.frozen
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.img_encoder.parameters()):
+        grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.img_encoder.parameters())
+        if self.is_vit:          # (no BatchNorm: training and eval compute the same thing, and there are no counters to bump)
+            if grad:
+                x = _ViTFn.apply(image, rt.anchor, self, rt, training)
+            else:
+                x, _ = vit_forward(rt, self.img_encoder, image.to(torch.float32).contiguous(), training)
+        elif grad:
             x = _ResNetFn.apply(image, rt.anchor, self, rt, training)
         else:
             x, _ = resnet_forward(rt, self.img_encoder, image.to(torch.float32).contiguous(), training)
@@ -63,6 +90,9 @@ class ImageEncoder(nn.Module):
 
     def detectron2_backbone_state_dict(self) -> Dict[str, Any]:
         """Same renaming as reference encoder.py:67-112 (torchvision names -> Detectron2 names)."""
+        if self.is_vit:
+            raise NotImplementedError("detectron2_backbone_state_dict: the Detectron2 export renames a ResNet's stages (res2 .. res5); a ViT image "
+                                      "encoder has none")
         mapping = {"layer1": "res2", "layer2": "res3", "layer3": "res4", "layer4": "res5", "bn1": "conv1.norm", "bn2": "conv2.norm",
                    "bn3": "conv3.norm", "downsample.0": "shortcut", "downsample.1": "shortcut.norm"}
         out = {}

@@ -146,8 +146,13 @@ class VisualBackboneFactory(Factory):
 
     @classmethod
     def from_config(cls, config: Config) -> ImageEncoder:
-        # like the reference (factories.py:324-327) only the network name is forwarded
-        return cls.create(config.MODEL.NAME, img_enc_net=config.MODEL.VISUAL.NETWORK_NAME)
+        # like the reference (factories.py:324-327) the network name is forwarded; a ViT is also built for one image size (its position embedding)
+        _C = config
+        enc = cls.create(_C.MODEL.NAME, img_enc_net=_C.MODEL.VISUAL.NETWORK_NAME, image_size=_C.DATA.IMAGE_CROP_SIZE)
+        if enc.out_dim != _C.MODEL.VISUAL.FEATURE_SIZE:
+            raise ValueError(f"MODEL.VISUAL.FEATURE_SIZE is {_C.MODEL.VISUAL.FEATURE_SIZE}, but {_C.MODEL.VISUAL.NETWORK_NAME} produces "
+                             f"{enc.out_dim} features; set MODEL.VISUAL.FEATURE_SIZE to {enc.out_dim}")
+        return enc
 
 
 class TextualHeadFactory(Factory):

@@ -192,6 +192,11 @@ _SIGNATURES = {
     "clite_lars_step": [_V, _V, _V, _V, _V, _V, _I, _V, _V, _V, _I, _V],
     "clite_debias_pca": [_V, _I, _I, _I, _V, _V, _V, _V, _V],
     "clite_debias_rows": [_V, _V, _I, _I, _I, _V, _V, _V, _V],
+    "clite_vit_patchify": [_I, _V, _V, _I, _I, _I, _I, _V],
+    "clite_vit_tokens_fwd": [_I, _V, _V, _V, _V, _I, _I, _I, _V],
+    "clite_vit_tokens_bwd": [_I, _V, _V, _V, _V, _I, _I, _I, _V],
+    "clite_vit_class_gather": [_I, _V, _V, _I, _I, _I, _V],
+    "clite_vit_class_scatter": [_I, _V, _V, _I, _I, _I, _V],
 }
 
 _lib = None
@@ -913,6 +918,43 @@ def mean_pool_bwd(dt, dy, mask, inv, dh, B, L, Cc):
 
 def tanh_bwd(dt, dy, y, out, n):
     check(lib().clite_tanh_bwd(dt, p(dy), p(y), p(out), n, stream_ptr(dy)), "tanh_bwd")
+
+
+# ------------------------------------------------------------------------------------------------ ViT pieces (clip_lite_amd/vit.py)
+def vit_patchify(dt, img, out, B, H, W, p_):
+    """img f32 NCHW [B][3][H][W] -> out [B * (H/p) * (W/p)][3 * p * p] of the compute dtype, columns (c, i, j) (include/clite.h: clite_vit_patchify)."""
+    if img.dtype != torch.float32 or tuple(img.shape) != (B, 3, H, W) or not img.is_contiguous():
+        raise ValueError(f"vit_patchify: img must be a contiguous f32 tensor of shape {(B, 3, H, W)}")
+    if H % p_ or W % p_ or out.dtype != TORCH_DTYPE[dt] or out.numel() != B * 3 * H * W or not out.is_contiguous():
+        raise ValueError(f"vit_patchify: out must be a contiguous {TORCH_DTYPE[dt]} tensor of {B * 3 * H * W} elements and p divide H and W")
+    check(lib().clite_vit_patchify(dt, p(img), p(out), B, H, W, p_, stream_ptr(img)), "vit_patchify")
+
+
+def vit_tokens_fwd(dt, e, cls, pos, s0, B, P, Cc):
+    """s0 [B * (P + 1)][C] = class token / patch embeddings e [B * P][C] + position embedding (include/clite.h: clite_vit_tokens_fwd)."""
+    assert e.numel() == B * P * Cc and cls.numel() == Cc and pos.numel() == (P + 1) * Cc and s0.numel() == B * (P + 1) * Cc
+    assert all(t.dtype == TORCH_DTYPE[dt] and t.is_contiguous() for t in (e, cls, pos, s0))
+    check(lib().clite_vit_tokens_fwd(dt, p(e), p(cls), p(pos), p(s0), B, P, Cc, stream_ptr(e)), "vit_tokens_fwd")
+
+
+def vit_tokens_bwd(dt, ds0, de, dpos, dcls, B, P, Cc):
+    """de [B * P][C] = the patch rows of ds0; dpos f32 [P + 1][C] and dcls f32 [C] (either may be None) += the sums over the batch, added in index
+    order by one thread per slot (include/clite.h: clite_vit_tokens_bwd)."""
+    assert ds0.numel() == B * (P + 1) * Cc and de.numel() == B * P * Cc and ds0.dtype == de.dtype == TORCH_DTYPE[dt]
+    assert ds0.is_contiguous() and de.is_contiguous()
+    assert dpos is None or (dpos.dtype == torch.float32 and dpos.numel() == (P + 1) * Cc and dpos.is_contiguous())
+    assert dcls is None or (dcls.dtype == torch.float32 and dcls.numel() == Cc and dcls.is_contiguous())
+    check(lib().clite_vit_tokens_bwd(dt, p(ds0), p(de), p(dpos), p(dcls), B, P, Cc, stream_ptr(ds0)), "vit_tokens_bwd")
+
+
+def vit_class_gather(dt, x, out, B, L, Cc):
+    assert x.numel() == B * L * Cc and out.numel() == B * Cc and x.dtype == out.dtype == TORCH_DTYPE[dt] and x.is_contiguous() and out.is_contiguous()
+    check(lib().clite_vit_class_gather(dt, p(x), p(out), B, L, Cc, stream_ptr(x)), "vit_class_gather")
+
+
+def vit_class_scatter(dt, d, dx, B, L, Cc):
+    assert dx.numel() == B * L * Cc and d.numel() == B * Cc and d.dtype == dx.dtype == TORCH_DTYPE[dt] and d.is_contiguous() and dx.is_contiguous()
+    check(lib().clite_vit_class_scatter(dt, p(d), p(dx), B, L, Cc, stream_ptr(d)), "vit_class_scatter")
 
 
 # ------------------------------------------------------------------------------------------------ loss / update

@@ -14,9 +14,15 @@ from . import hip
 ALIGN = 64  # elements; keeps every tensor 256-byte aligned and QKV groups exactly contiguous
 
 
+def _krsc(p):
+    """Is this a convolution weight kept [K][R][S][C]? Every 4-D tensor but those marked `_clite_plain` (the ViT's patch projection, vit.py: its GEMM
+    reads torch's own [K][C][R][S] order)."""
+    return p.dim() == 4 and not getattr(p, "_clite_plain", False)
+
+
 def _kernel_shape(p):
     """Shape of the tensor as the kernels see it (conv weights KCRS -> KRSC)."""
-    if p.dim() == 4:
+    if _krsc(p):
         K, Cc, R, S = p.shape
         return (K, R, S, Cc)
     return tuple(p.shape)
@@ -71,7 +77,7 @@ class Arena:
             o, numel = self.index[n]
             ks = _kernel_shape(p)
             src = p.detach().to(device=device, dtype=torch.float32)
-            if p.dim() == 4:
+            if _krsc(p):
                 src = src.permute(0, 2, 3, 1)
             self.flat_p[o:o + numel].view(ks).copy_(src)
             p.data = self._torch_view(self.flat_p, o, numel, p)
@@ -82,7 +88,7 @@ class Arena:
 
     @staticmethod
     def _torch_view(flat, o, numel, p):
-        if p.dim() == 4:
+        if _krsc(p):
             K, Cc, R, S = p.shape
             return flat[o:o + numel].view(K, R, S, Cc).permute(0, 3, 1, 2)
         return flat[o:o + numel].view(p.shape)
@@ -194,7 +200,7 @@ class Arena:
                 N, K = p.shape
                 add(o, N, K, K, N, 1, 0, 0)
                 self._tr_shape[id(p)] = (o, (K, N))
-            elif p.dim() == 4 and p.shape[0] % 8 == 0 and p.shape[1] % 8 == 0:
+            elif _krsc(p) and p.shape[0] % 8 == 0 and p.shape[1] % 8 == 0:
                 K, Cc, R, S = p.shape
                 add(o, K, Cc, R * S * Cc, R * S * K, R * S, Cc, K)
                 self._tr_shape[id(p)] = (o, (Cc, R, S, K))
@@ -295,6 +301,9 @@ class DeviceRuntime:
             tw = [m.weight for top in ("image_encoder", "text_encoder") if hasattr(model, top) for m in getattr(model, top).modules()
                   if isinstance(getattr(m, "weight", None), torch.nn.Parameter) and hasattr(m.weight, "_clite")
                   and (hasattr(m, "in_features") or hasattr(m, "in_channels"))]
+            # ... and the bare 2-D parameters a module names itself (vit._SelfAttention.in_proj_weight)
+            tw += [w for top in ("image_encoder", "text_encoder") if hasattr(model, top) for m in getattr(model, top).modules()
+                   if hasattr(m, "dgrad_weights") for w in m.dgrad_weights() if hasattr(w, "_clite")]
             tg = [[by_name[n] for n in g] for g in contiguous_groups if all(n in by_name for n in g) and by_name[g[0]].dim() == 2]
             self.arena.register_transposed(tw, tg)
         self.base_seed = int(seed)

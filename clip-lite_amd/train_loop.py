@@ -193,7 +193,10 @@ class TrainStep:
         m = self.model
         inert = self._inert_params()
         from .loss import GlobalDiscriminatorDot
+        from .resnet import ResNet
+        # (the per-phase graphs are scheduled around the ResNet's backward segments; a ViT image encoder takes the whole step as one graph)
         return (getattr(m, "mode", None) == "train_sbert" and not m.text_encoder.transform_embedding and m.training
+                and isinstance(getattr(m.image_encoder, "img_encoder", None), ResNet)
                 and isinstance(m.loss.global_d, GlobalDiscriminatorDot)
                 and not getattr(m.image_encoder, "frozen", False)
                 and all(p.requires_grad for p in m.parameters() if id(p) not in inert))

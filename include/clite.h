@@ -825,6 +825,25 @@ int clite_debias_pca(const float* diffs, int P, int D, int R, float* eigvals, fl
  * misaligned x, components, xn or xd. */
 int clite_debias_rows(const float* x, const float* components, int N, int D, int R, float* xn, float* xd, float* coef, void* stream);
 
+/* ---- ViT image encoder (torchvision.models.vit_b_32 / vit_b_16 as the reference's ImageEncoder would build them; clip-lite_amd/vit.py):
+ * what the tower needs beside the GEMMs, clite_layernorm_* and clite_attention_*. Additive to ABI v12. Streaming kernels, 16-byte accesses, no
+ * float atomics: each result is a pure function of its inputs in both settings of clite_set_deterministic. Every pointer 16-byte aligned;
+ * a violated precondition returns -1 and launches nothing. */
+/* The patch matrix of an image batch: img f32 NCHW [B][3][H][W] (H % p == 0, W % p == 0, p % 8 == 0) ->
+ * out [B * (H/p) * (W/p)][3 * p * p] in `dtype`, row (b, ph, pw) row-major, column (c, i, j) = img[b][c][ph p + i][pw p + j]: the column order
+ * of nn.Conv2d(3, C, p, stride = p).weight.view(C, 3 p p), which is then clite_gemm_nt's B operand as it is. The image has no gradient. */
+int clite_vit_patchify(int dtype, const float* img, void* out, int B, int H, int W, int p, void* stream);
+/* Token assembly, L = P + 1 tokens of C elements (C % 8 == 0): s0[b][0] = cls + pos[0], s0[b][1 + t] = e[b][t] + pos[1 + t]; e [B * P][C] is the
+ * patch GEMM's output (conv_proj.bias added by its epilogue), cls [C], pos [L][C], all of `dtype`; the sum is formed in f32 and rounded once. */
+int clite_vit_tokens_fwd(int dtype, const void* e, const void* cls, const void* pos, void* s0, int B, int P, int C, void* stream);
+/* Its backward: de[b][t] = ds0[b][1 + t] (`dtype`), dpos[t] += sum_b ds0[b][t] and dcls += sum_b ds0[b][0] (f32, either may be NULL). One
+ * thread owns a (token, 8 columns) slot and adds over b in index order. */
+int clite_vit_tokens_bwd(int dtype, const void* ds0, void* de, float* dpos, float* dcls, int B, int P, int C, void* stream);
+/* The class rows around the final LayerNorm (which acts row by row, so only they need it): out[b] = x[b * L] of x [B * L][C]; and the
+ * backward, dx[b * L] = d[b], the other rows of dx left as they are (the caller zeroes them). */
+int clite_vit_class_gather(int dtype, const void* x, void* out, int B, int L, int C, void* stream);
+int clite_vit_class_scatter(int dtype, const void* d, void* dx, int B, int L, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
