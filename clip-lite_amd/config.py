@@ -165,6 +165,11 @@ class Config(object):
         _C.OPTIM.LARS = Node()          # OPTIMIZER_NAME "lars": SGD (SGD_MOMENTUM) with per-tensor trust ratios (optim.FusedLARS)
         _C.OPTIM.LARS.TRUST_COEFFICIENT = 0.001
         _C.OPTIM.LARS.EPS = 1e-8
+        _C.OPTIM.LAMB = Node()          # OPTIMIZER_NAME "lamb": AdamW moments with per-tensor trust ratios |p| / |r| (optim.FusedLAMB)
+        _C.OPTIM.LAMB.BETA1 = 0.9
+        _C.OPTIM.LAMB.BETA2 = 0.999
+        _C.OPTIM.LAMB.EPS = 1e-6
+        _C.OPTIM.LAMB.TRUST_CLIP = False          # cap the trust ratio at 1
         _C.OPTIM.BATCH_SIZE = 256
         _C.OPTIM.CNN_LR = 0.2
         _C.OPTIM.LR = 0.001

@@ -5,6 +5,7 @@
 // the update moves what the SGD update moves.
 #include "vec.h"
 #include "clite.h"
+#include "norm_fold.h"
 
 using namespace clite;
 
@@ -37,30 +38,7 @@ __global__ __launch_bounds__(256) void lars_partial_kernel(const float* __restri
   }
 }
 
-// Stage 2: the workgroup of a tensor's FIRST item folds that tensor's pairs; every other workgroup leaves at once. Thread t adds the pairs of
-// the tensor's items t, t + 256, ... in that order (a tensor's items are contiguous in the table, so a thread stops at the first item of
-// another slot), then the fixed wave / workgroup fold. The order depends on the tensor's own items only: a launch of a sub-range of the table
-// that holds the tensor whole gives the same bits as a launch of the whole table. The embedding's 2862 pairs take 12 trips.
-__global__ __launch_bounds__(256) void lars_fold_kernel(const clite_optim_item* __restrict__ items, uint32_t n_items, const float* __restrict__ partials,
-                                                        float* __restrict__ norms, uint32_t n_slots) {
-  __shared__ float red[2][4];
-  const uint32_t head = blockIdx.x, slot1 = items[head].reserved;
-  if (slot1 == 0 || slot1 > n_slots) return;
-  if (head > 0 && items[head - 1].reserved == slot1) return;
-  float sp = 0.f, sg = 0.f;
-  for (uint32_t j = head + threadIdx.x; j < n_items && items[j].reserved == slot1; j += 256) {
-    sp += partials[2 * (size_t)j];
-    sg += partials[2 * (size_t)j + 1];
-  }
-  sp = wave_sum(sp);
-  sg = wave_sum(sg);
-  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = sp; red[1][threadIdx.x >> 6] = sg; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    norms[2 * (size_t)(slot1 - 1)] = (red[0][0] + red[0][1]) + (red[0][2] + red[0][3]);
-    norms[2 * (size_t)(slot1 - 1) + 1] = (red[1][0] + red[1][1]) + (red[1][2] + red[1][3]);
-  }
-}
+// Stage 2 is norm_fold_kernel (norm_fold.h, shared with lamb_ops.hip): the workgroup of a tensor's first item folds that tensor's pairs in item order.
 
 // hp: as sgd_step_kernel, plus [6] trust coefficient eta, [7] eps. The trust ratio is formed once per workgroup from block-uniform values and
 // folded into the two scalars of the gradient term: q (g gmul + wd p) = g (gmul q) + (wd q) p. The loop below is sgd_step_kernel's loop, statement
@@ -120,7 +98,7 @@ extern "C" int clite_lars_norms(const float* p, const float* g, const clite_opti
   if (!p || !g || !items || n_items <= 0 || !partials || !norms || n_slots < 0) return -1;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(lars_partial_kernel, dim3(n_items), dim3(256), 0, st, p, g, items, partials, (uint32_t)n_slots);
-  hipLaunchKernelGGL(lars_fold_kernel, dim3(n_items), dim3(256), 0, st, items, (uint32_t)n_items, (const float*)partials, norms, (uint32_t)n_slots);
+  hipLaunchKernelGGL(norm_fold_kernel, dim3(n_items), dim3(256), 0, st, items, (uint32_t)n_items, (const float*)partials, norms, (uint32_t)n_slots);
   return (int)hipGetLastError();
 }
 

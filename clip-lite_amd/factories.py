@@ -13,7 +13,7 @@ from .config import Config
 from .encoder import ImageEncoder, TextEncoder
 from .loss import InfoNCELoss, JSDInfoMaxLoss
 from .model import VLInfoModel
-from .optim import FusedAdamW, FusedLARS, FusedSGD, Lookahead, lr_scheduler
+from .optim import FusedAdamW, FusedLAMB, FusedLARS, FusedSGD, Lookahead, lr_scheduler
 
 
 class Factory(object):
@@ -198,7 +198,7 @@ class PretrainingModelFactory(Factory):
 
 
 class OptimizerFactory(Factory):
-    PRODUCTS: Dict[str, Callable] = {"sgd": FusedSGD, "adamw": FusedAdamW, "lars": FusedLARS}
+    PRODUCTS: Dict[str, Callable] = {"sgd": FusedSGD, "adamw": FusedAdamW, "lars": FusedLARS, "lamb": FusedLAMB}
 
     @classmethod
     def from_config(cls, config: Config, named_parameters: Iterable[Any]):
@@ -216,6 +216,8 @@ class OptimizerFactory(Factory):
         kwargs = {"momentum": _C.OPTIM.SGD_MOMENTUM} if _C.OPTIM.OPTIMIZER_NAME in ("sgd", "lars") else {}          # (reference factories.py:478-483)
         if _C.OPTIM.OPTIMIZER_NAME == "lars":
             kwargs.update(trust_coefficient=_C.OPTIM.LARS.TRUST_COEFFICIENT, eps=_C.OPTIM.LARS.EPS)
+        if _C.OPTIM.OPTIMIZER_NAME == "lamb":
+            kwargs.update(betas=(_C.OPTIM.LAMB.BETA1, _C.OPTIM.LAMB.BETA2), eps=_C.OPTIM.LAMB.EPS, trust_clip=_C.OPTIM.LAMB.TRUST_CLIP)
         optimizer = cls.create(_C.OPTIM.OPTIMIZER_NAME, param_groups, **kwargs)
         if _C.OPTIM.LOOKAHEAD.USE:
             optimizer = Lookahead(optimizer, k=_C.OPTIM.LOOKAHEAD.STEPS, alpha=_C.OPTIM.LOOKAHEAD.ALPHA)

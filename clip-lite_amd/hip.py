@@ -190,6 +190,8 @@ _SIGNATURES = {
     "clite_cast_bf16": [_V, _V, _U64, _V],
     "clite_lars_norms": [_V, _V, _V, _I, _V, _V, _I, _V],
     "clite_lars_step": [_V, _V, _V, _V, _V, _V, _I, _V, _V, _V, _I, _V],
+    "clite_lamb_moments": [_V, _V, _V, _V, _V, _I, _V, _V, _V, _V, _I, _V],
+    "clite_lamb_step": [_V, _V, _V, _V, _V, _V, _V, _I, _V, _V, _V, _I, _V],
     "clite_debias_pca": [_V, _I, _I, _I, _V, _V, _V, _V, _V],
     "clite_debias_rows": [_V, _V, _I, _I, _I, _V, _V, _V, _V],
     "clite_vit_patchify": [_I, _V, _V, _I, _I, _I, _I, _V],
@@ -1088,6 +1090,24 @@ def lars_norms(pf, gf, items_ptr, n_items, partials, norms):
 def lars_step(pf, gf, vf, slow, cast, items_ptr, n_items, hp, ss, norms):
     check(lib().clite_lars_step(p(pf), p(gf), p(vf), p(slow), p(cast), items_ptr, n_items, p(hp), p(ss), p(norms), norms.numel() // 2,
                                 stream_ptr(pf)), "lars_step")
+
+
+def lamb_moments(pf, gf, mf, v2f, items_ptr, n_items, hp, ss, partials, norms):
+    """m, v2 of the launched items updated in place; norms [slots][2] = (sum p^2, sum r^2) of their adapted tensors, r from the updated moments.
+    partials: f32, two per launched item."""
+    if partials.numel() < 2 * n_items:
+        raise RuntimeError("lamb_moments: partials holds fewer than two floats per item")
+    if hp.numel() < 13:
+        raise RuntimeError("lamb_moments: hp holds fewer than 13 floats")
+    check(lib().clite_lamb_moments(p(pf), p(gf), p(mf), p(v2f), items_ptr, n_items, p(hp), p(ss), p(partials), p(norms), norms.numel() // 2,
+                                   stream_ptr(pf)), "lamb_moments")
+
+
+def lamb_step(pf, gf, mf, v2f, slow, cast, items_ptr, n_items, hp, ss, norms):
+    if hp.numel() < 13:
+        raise RuntimeError("lamb_step: hp holds fewer than 13 floats")
+    check(lib().clite_lamb_step(p(pf), p(gf), p(mf), p(v2f), p(slow), p(cast), items_ptr, n_items, p(hp), p(ss), p(norms), norms.numel() // 2,
+                                stream_ptr(pf)), "lamb_step")
 
 
 def adamw_step(pf, gf, mf, v2f, slow, cast, items_ptr, n_items, hp, ss):

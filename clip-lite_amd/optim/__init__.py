@@ -1,2 +1,2 @@
-from .fused_sgd import FusedAdamW, FusedLARS, FusedSGD, Lookahead  # noqa: F401
+from .fused_sgd import FusedAdamW, FusedLAMB, FusedLARS, FusedSGD, Lookahead  # noqa: F401
 from . import lr_scheduler  # noqa: F401

@@ -6,6 +6,7 @@ wrapped in optim/lookahead.py:35-101's Lookahead(k, alpha). `state_dict()` keeps
 (`momentum_buffer` per parameter), and — like the reference (lookahead.py:68-78) — the slow weights are not serialized but
 re-seeded from the fast weights on load.
 """
+import bisect
 import ctypes as C
 from typing import Any, Callable, Dict
 
@@ -144,12 +145,17 @@ class FusedSGD(torch.optim.Optimizer):
         mom = self.param_groups[0]["momentum"]
         mn = self.max_norm if max_norm is None else float(max_norm)
         vals = [self._lr_mult(), mom, mn, 1.0 if lookahead_sync else 0.0, alpha, self.grad_prescale, 0.0, 0.0]
+        self._upload(vals)
+
+    def _upload(self, vals):
+        """`vals` (padded with zeros to the length of `hp`) -> device `hp`, without a host synchronisation in the steady state."""
+        vals = list(vals) + [0.0] * (self.hp.numel() - len(vals))
         if not self.hp.is_cuda:
             self.hp.copy_(torch.tensor(vals))
             return
         # asynchronous upload from a small ring of pinned slots: a slot is rewritten only after the copy that read it has executed
         if self._hp_ring is None:
-            self._hp_ring = [(torch.empty(8, dtype=torch.float32).pin_memory(), torch.cuda.Event()) for _ in range(8)]
+            self._hp_ring = [(torch.empty(self.hp.numel(), dtype=torch.float32).pin_memory(), torch.cuda.Event()) for _ in range(8)]
             self._hp_used = [False] * 8
             self._hp_next = 0
         i = self._hp_next
@@ -166,18 +172,22 @@ class FusedSGD(torch.optim.Optimizer):
         for lo, hi in getattr(self, "_frozen_spans", ()):
             self.arena.flat_g[lo:hi].zero_()
 
-    @torch.no_grad()
-    def launch(self, span=None):
-        """span = (lo, hi): update only the tensors whose arena offset lies in [lo, hi) — the captured step updates the image encoder at the end
-        of a step and the rest at the start of the next one (train_loop.TrainStep, defer_update); every tensor exactly once per step."""
+    def _launch_range(self, span):
+        """What every launch() does first; returns (first item, number of items) of `span` (None: the whole table)."""
         self.arena.join()
         self._build_items()
         self.zero_frozen()
         first, n = 0, self._n_items
         if span is not None:
-            import bisect
             first = bisect.bisect_left(self._item_starts, span[0])
             n = bisect.bisect_left(self._item_starts, span[1]) - first
+        return first, n
+
+    @torch.no_grad()
+    def launch(self, span=None):
+        """span = (lo, hi): update only the tensors whose arena offset lies in [lo, hi) — the captured step updates the image encoder at the end
+        of a step and the rest at the start of the next one (train_loop.TrainStep, defer_update); every tensor exactly once per step."""
+        first, n = self._launch_range(span)
         if n > 0:
             hip.sgd_step(self.arena.flat_p, self.arena.flat_g, self.flat_v, self.flat_slow, self.arena.flat_lp,
                          C.c_void_p(self._items.data_ptr() + first * C.sizeof(hip.OptimItem)), n, self.hp, self.sumsq)
@@ -210,32 +220,25 @@ class FusedSGD(torch.optim.Optimizer):
         self._items_key = None
 
 
-class FusedLARS(FusedSGD):
-    """LARS (You, Gitman, Ginsburg 2017; the update SimCLR-style recipes run at batch sizes of 1k .. 32k) on FusedSGD's arena, work items, clipping,
-    Lookahead hook, captured-step protocol and checkpoint layout (torch SGD's `momentum_buffer`, which is what LARS wrappers around torch.optim.SGD
-    save): for every trainable tensor of two or more dimensions the SGD gradient term g' + wd p is scaled by the trust ratio
-    trust_coefficient |p| / (|g'| + wd |p| + eps), where g' is the pre-scaled, clipped gradient (1 where either norm is zero); biases and
-    normalisation scales (ndim <= 1) move exactly as under FusedSGD. The per-tensor norms are two launches over the item table
-    (clite_lars_norms: fixed order, no float atomics), the update one (clite_lars_step); launch(span) takes the norms of the span it updates."""
+class _PerTensorNorms:
+    """What the layer-wise optimizers (FusedLARS, FusedLAMB) share: a norm slot per trainable tensor of two or more dimensions, the `reserved` word
+    of that tensor's items (slot + 1; 0 = not adapted: biases, normalisation scales), and the buffers of the two-stage norm reduction."""
 
-    def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0, trust_coefficient=0.001, eps=1e-8):
-        super().__init__(params, lr=lr, momentum=momentum, weight_decay=weight_decay)
-        self.trust_coefficient, self.eps = float(trust_coefficient), float(eps)
+    def _init_norms(self):
         plist = [p for g in self.param_groups for p in g["params"]]
         adapted = [p for p in plist if p.dim() >= 2]
         self._slots = {id(p): i for i, p in enumerate(adapted)}
         self._spans = {self.arena.index[p._clite[1]][0]: self.arena.index[p._clite[1]][1] for p in adapted}      # arena offset -> elements
         dev = self.arena.device
-        self.norms = torch.zeros(max(len(adapted), 1), 2, device=dev, dtype=torch.float32)      # (sum p^2, sum g^2) per adapted tensor
+        self.norms = torch.zeros(max(len(adapted), 1), 2, device=dev, dtype=torch.float32)      # a pair of squared norms per adapted tensor
         n_items = sum(((self.arena.index[p._clite[1]][1] + 3) // 4 * 4 + CHUNK - 1) // CHUNK for p in plist)
-        self.norm_partials = torch.zeros(2 * max(n_items, 1), device=dev, dtype=torch.float32)  # clite_lars_norms' first stage: a pair per item
+        self.norm_partials = torch.zeros(2 * max(n_items, 1), device=dev, dtype=torch.float32)  # the reduction's first stage: a pair per item
 
     def _build_items(self):
-        """FusedSGD's table, then the `reserved` word of every item of an adapted tensor: that tensor's norm slot + 1."""
+        """The base class's table, then the `reserved` word of every item of an adapted tensor: that tensor's norm slot + 1."""
         if self._base_lrs() == self._items_key:
             return
         super()._build_items()
-        import bisect
         owners = sorted((self.arena.index[p._clite[1]][0], self._slots[id(p)] + 1) for g in self.param_groups for p in g["params"] if id(p) in self._slots)
         offs = [o for o, _ in owners]
         arr = (hip.OptimItem * self._n_items).from_buffer_copy(self._items.cpu().numpy().tobytes())
@@ -245,42 +248,35 @@ class FusedLARS(FusedSGD):
                 arr[i].reserved = owners[k][1]
         self._items = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.arena.device)
 
+    def tensor_norms(self, p):
+        """The two norms of an adapted parameter as the last launch that updated it measured them."""
+        return tuple(self.norms[self._slots[id(p)]].double().sqrt().tolist())
+
+
+class FusedLARS(_PerTensorNorms, FusedSGD):
+    """LARS (You, Gitman, Ginsburg 2017; the update SimCLR-style recipes run at batch sizes of 1k .. 32k) on FusedSGD's arena, work items, clipping,
+    Lookahead hook, captured-step protocol and checkpoint layout (torch SGD's `momentum_buffer`, which is what LARS wrappers around torch.optim.SGD
+    save): for every trainable tensor of two or more dimensions the SGD gradient term g' + wd p is scaled by the trust ratio
+    trust_coefficient |p| / (|g'| + wd |p| + eps), where g' is the pre-scaled, clipped gradient (1 where either norm is zero); biases and
+    normalisation scales (ndim <= 1) move exactly as under FusedSGD. The per-tensor norms are two launches over the item table
+    (clite_lars_norms: fixed order, no float atomics), the update one (clite_lars_step); launch(span) takes the norms of the span it updates.
+    tensor_norms(p) is (|p|, |g|), of the raw gradient: before pre-scale and clipping."""
+
+    def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0, trust_coefficient=0.001, eps=1e-8):
+        super().__init__(params, lr=lr, momentum=momentum, weight_decay=weight_decay)
+        self.trust_coefficient, self.eps = float(trust_coefficient), float(eps)
+        self._init_norms()
+
     def upload_hp(self, lookahead_sync=False, alpha=1.0, max_norm=None):
         """FusedSGD.upload_hp with the trust coefficient and eps in slots 6 and 7."""
         mom = self.param_groups[0]["momentum"]
         mn = self.max_norm if max_norm is None else float(max_norm)
         vals = [self._lr_mult(), mom, mn, 1.0 if lookahead_sync else 0.0, alpha, self.grad_prescale, self.trust_coefficient, self.eps]
-        if not self.hp.is_cuda:
-            self.hp.copy_(torch.tensor(vals))
-            return
-        if self._hp_ring is None:
-            self._hp_ring = [(torch.empty(8, dtype=torch.float32).pin_memory(), torch.cuda.Event()) for _ in range(8)]
-            self._hp_used = [False] * 8
-            self._hp_next = 0
-        i = self._hp_next
-        self._hp_next = (i + 1) % len(self._hp_ring)
-        host, ev = self._hp_ring[i]
-        if self._hp_used[i]:
-            ev.synchronize()
-        host.copy_(torch.tensor(vals))
-        self.hp.copy_(host, non_blocking=True)
-        ev.record()
-        self._hp_used[i] = True
-
-    def tensor_norms(self, p):
-        """(|p|, |g|) of an adapted parameter as the last launch that updated it measured them (raw gradient: before pre-scale and clipping)."""
-        return tuple(self.norms[self._slots[id(p)]].double().sqrt().tolist())
+        self._upload(vals)
 
     @torch.no_grad()
     def launch(self, span=None):
-        self.arena.join()
-        self._build_items()
-        self.zero_frozen()
-        first, n = 0, self._n_items
-        if span is not None:
-            import bisect
-            first = bisect.bisect_left(self._item_starts, span[0])
-            n = bisect.bisect_left(self._item_starts, span[1]) - first
+        first, n = self._launch_range(span)
         if n > 0:
             items = C.c_void_p(self._items.data_ptr() + first * C.sizeof(hip.OptimItem))
             # every span has its own share of the partials: two spans may be in flight on two streams (TrainStep: update_img / update_rest)
@@ -325,34 +321,16 @@ class FusedAdamW(FusedSGD):
         b1, b2 = self.param_groups[0]["betas"]
         mn = self.max_norm if max_norm is None else float(max_norm)
         vals = [self._lr_mult(), b1, mn, 1.0 if lookahead_sync else 0.0, alpha, self.grad_prescale, b2, self.param_groups[0]["eps"],
-                1.0 - b1 ** self.steps, 1.0 - b2 ** self.steps, 1.0 - b1, 1.0 - b2]
-        if not self.hp.is_cuda:
-            self.hp.copy_(torch.tensor(vals))
-            return
-        if self._hp_ring is None:
-            self._hp_ring = [(torch.empty(12, dtype=torch.float32).pin_memory(), torch.cuda.Event()) for _ in range(8)]
-            self._hp_used = [False] * 8
-            self._hp_next = 0
-        i = self._hp_next
-        self._hp_next = (i + 1) % len(self._hp_ring)
-        host, ev = self._hp_ring[i]
-        if self._hp_used[i]:
-            ev.synchronize()
-        host.copy_(torch.tensor(vals))
-        self.hp.copy_(host, non_blocking=True)
-        ev.record()
-        self._hp_used[i] = True
+                1.0 - b1 ** self.steps, 1.0 - b2 ** self.steps, 1.0 - b1, 1.0 - b2] + self._hp_tail()
+        self._upload(vals)
+
+    def _hp_tail(self):
+        """What a subclass appends to the twelve floats of `hp`."""
+        return []
 
     @torch.no_grad()
     def launch(self, span=None):
-        self.arena.join()
-        self._build_items()
-        self.zero_frozen()
-        first, n = 0, self._n_items
-        if span is not None:
-            import bisect
-            first = bisect.bisect_left(self._item_starts, span[0])
-            n = bisect.bisect_left(self._item_starts, span[1]) - first
+        first, n = self._launch_range(span)
         if n > 0:
             hip.adamw_step(self.arena.flat_p, self.arena.flat_g, self.flat_v, self.flat_v2, self.flat_slow, self.arena.flat_lp,
                            C.c_void_p(self._items.data_ptr() + first * C.sizeof(hip.OptimItem)), n, self.hp, self.sumsq)
@@ -388,6 +366,43 @@ class FusedAdamW(FusedSGD):
                 if st.get("step") is not None:
                     self.steps = int(float(st["step"]))
         self._items_key = None
+
+
+class FusedLAMB(_PerTensorNorms, FusedAdamW):
+    """LAMB (You et al. 2020, "Large Batch Optimization for Deep Learning", Algorithm 2) on FusedAdamW's moments, step counter, clipping, Lookahead
+    hook, captured-step protocol and checkpoint layout (torch.optim.AdamW's step / exp_avg / exp_avg_sq): with r = m^ / (sqrt(v^) + eps) + wd p
+    from this step's bias-corrected moments, every trainable tensor of two or more dimensions moves by lr q r, q = |p| / |r| (1 where either norm
+    is zero; capped at 1 with trust_clip), biases and normalisation scales (ndim <= 1) exactly as under FusedAdamW. Bias correction is always on;
+    there is no eps in q and no trust coefficient. Two launches per span: clite_lamb_moments (moments in place, the per-tensor norms in a fixed
+    order, no float atomics) and clite_lamb_step. tensor_norms(p) is (|p| before the update, |r|)."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, trust_clip=False):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
+        self.trust_clip = bool(trust_clip)
+        self.hp = torch.zeros(16, device=self.arena.device, dtype=torch.float32)          # FusedAdamW's twelve, [12] the TRUST_CLIP flag
+        self._init_norms()
+
+    def _hp_tail(self):
+        return [1.0 if self.trust_clip else 0.0]
+
+    def trust_ratio(self, p):
+        """q of an adapted parameter in the last launch that updated it."""
+        pn, rn = self.tensor_norms(p)
+        q = pn / rn if pn > 0 and rn > 0 else 1.0
+        return min(q, 1.0) if self.trust_clip else q
+
+    @torch.no_grad()
+    def launch(self, span=None):
+        first, n = self._launch_range(span)
+        if n > 0:
+            items = C.c_void_p(self._items.data_ptr() + first * C.sizeof(hip.OptimItem))
+            A = self.arena
+            # every span has its own share of the partials: two spans may be in flight on two streams (TrainStep: update_img / update_rest)
+            hip.lamb_moments(A.flat_p, A.flat_g, self.flat_v, self.flat_v2, items, n, self.hp, self.sumsq, self.norm_partials[2 * first:2 * (first + n)],
+                             self.norms)
+            hip.lamb_step(A.flat_p, A.flat_g, self.flat_v, self.flat_v2, self.flat_slow, A.flat_lp, items, n, self.hp, self.sumsq, self.norms)
+        self.arena._tr_stale = True
+        self._dirty = False
 
 
 class Lookahead(object):

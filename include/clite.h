@@ -758,7 +758,7 @@ typedef struct clite_optim_item {   /* one workgroup's slice of one parameter te
   uint32_t count;                   /* elements, multiple of 4 */
   float lr;                         /* base learning rate of the owning tensor's param group */
   float wd;                         /* weight decay of the owning tensor's param group */
-  uint32_t reserved;                /* clite_lars_*: slot of the owning tensor in `norms` + 1; 0 = not adapted (LARS). The other kernels ignore it. */
+  uint32_t reserved;                /* clite_lars_*, clite_lamb_*: slot of the owning tensor in `norms` + 1; 0 = not adapted. The other kernels ignore it. */
 } clite_optim_item;
 /* out (f32 scalar, pre-zeroed) += sum x^2 — the global gradient norm of clip_grad_norm_. Two fixed-order stages through `partials`
  * (device f32[n_partials], n_partials >= 1; 1024 slots use the whole chip): no float atomics, so the value is a pure function of x and every
@@ -799,6 +799,27 @@ int clite_lars_norms(const float* p, const float* g, const clite_optim_item* ite
                      void* stream);
 int clite_lars_step(float* p, float* g, float* v, float* slow, void* cast_bf16, const clite_optim_item* items, int n_items, const float* hp,
                     const float* sumsq, const float* norms, int n_slots, void* stream);
+/* LAMB (You et al. 2020, "Large Batch Optimization for Deep Learning", Algorithm 2) on the same item table, with clite_lars_*'s marking of adapted
+ * tensors through `reserved` and its two fixed-order norm stages. Additive to ABI v12. hp (device f32[13]): clite_adamw_step's twelve floats, then
+ * [12] = TRUST_CLIP flag. Per tensor, with g' = g prescale clip:
+ *   m += (1 - beta1)(g' - m); v2 = beta2 v2 + (1 - beta2) g'^2          (clite_adamw_step's statements)
+ *   r = (m / hp[8]) / (sqrt(v2 / hp[9]) + eps) + wd p
+ *   adapted: q = |p| / |r| if both norms > 0, else 1; with TRUST_CLIP q = min(q, 1); p -= lr mult q r
+ *   not adapted: p *= 1 - lr wd; p -= lr / hp[8] * m / (sqrt(v2) / sqrt(hp[9]) + eps), clite_adamw_step's arithmetic: with every reserved word 0
+ *   the two calls together give clite_adamw_step's p, m, v2, slow and bf16 copy bit for bit.
+ * |p| is taken before the update, |r| from the moments after it. There is no eps in q and no trust coefficient.
+ *
+ * clite_lamb_moments: updates m and v2 of every launched item in place and leaves norms[2 slot] = sum p^2, norms[2 slot + 1] = sum r^2 of every
+ * adapted tensor whose items lie in the launched table (partials: device f32[2 n_items], as clite_lars_norms; the same fold, so the same
+ * guarantees: no float atomics, bit-identical between runs, independent of which other tensors share the launch). p and g are not written.
+ *
+ * clite_lamb_step: re-forms r from the stored m, v2 and the unchanged p with the same device function (the r that was normed is the r that is
+ * applied, bit for bit), updates p, then the Lookahead sync, the zeroing of g and the bf16 copy as clite_adamw_step. Must follow clite_lamb_moments
+ * over the same items on the same stream. sumsq is not read (the clip factor entered the moments); it must not be null. */
+int clite_lamb_moments(const float* p, const float* g, float* m, float* v2, const clite_optim_item* items, int n_items, const float* hp,
+                       const float* sumsq, float* partials, float* norms, int n_slots, void* stream);
+int clite_lamb_step(float* p, float* g, const float* m, const float* v2, float* slow, void* cast_bf16, const clite_optim_item* items, int n_items,
+                    const float* hp, const float* sumsq, const float* norms, int n_slots, void* stream);
 
 /* ---- Bias evaluation: a direction found in the text embedding space, removed from image features (reference bias_eda.py, utils/we.py;
  * clip-lite_amd/debias.py). Additive to ABI v12. No float atomics: every result below is a pure function of its inputs, bit for bit. */
