@@ -1,5 +1,5 @@
 """Update path on the HIP kernels: global-norm clipping + SGD(momentum, weight decay, one group per tensor) + Lookahead
-in one pass over the flat parameter arena (csrc/optim_ops.hip).
+in one pass over the flat parameter arena (csrc/update_ops.hip).
 
 Mirrors the reference objects: torch.optim.SGD built with one param group per parameter (reference factories.py:464-482)
 wrapped in optim/lookahead.py:35-101's Lookahead(k, alpha). `state_dict()` keeps torch.optim.SGD's layout
@@ -17,19 +17,25 @@ from .. import hip
 CHUNK = 8192     # elements per workgroup of the update kernel
 
 
-class FusedSGD(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0):
-        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, dampening=0, nesterov=False))
+class _FusedUpdate(torch.optim.Optimizer):
+    """What the four fused optimizers share: the arena and the flat state buffers, the work-item table, global-norm clipping, the `hp` upload,
+    launch(span) and the torch-compatible checkpoint layout. A class adds its `hp` length and tail, its state buffers and the kernels it enqueues."""
+    HP_LEN = 8          # floats of `hp` (layout: csrc/update_ops.hip)
+    STATE = {}          # checkpoint key -> flat state buffer (attribute name; f32, one element per arena element)
+
+    def __init__(self, params, defaults):
+        super().__init__(params, defaults)
         plist = [p for g in self.param_groups for p in g["params"]]
         arenas = {id(p._clite[0]) for p in plist if hasattr(p, "_clite")}
         if len(arenas) != 1 or any(not hasattr(p, "_clite") for p in plist):
-            raise RuntimeError("FusedSGD: parameters must live in one device arena — move the model to the GPU (model.to(device)) "
+            raise RuntimeError(f"{type(self).__name__}: parameters must live in one device arena — move the model to the GPU (model.to(device)) "
                                "before building the optimizer, as reference train.py:136-138 does")
         self.arena = plist[0]._clite[0]
         dev = self.arena.device
-        self.flat_v = torch.zeros(self.arena.total, device=dev, dtype=torch.float32)
+        for name in self.STATE.values():
+            setattr(self, name, torch.zeros(self.arena.total, device=dev, dtype=torch.float32))
         self.flat_slow = self.arena.flat_p.clone()
-        self.hp = torch.zeros(8, device=dev, dtype=torch.float32)
+        self.hp = torch.zeros(self.HP_LEN, device=dev, dtype=torch.float32)
         self.sumsq = torch.zeros(1, device=dev, dtype=torch.float32)
         self.sumsq_partials = torch.zeros(1024, device=dev, dtype=torch.float32)      # clite_sumsq's fixed-order first stage
         self.max_norm = 0.0
@@ -55,7 +61,7 @@ class FusedSGD(torch.optim.Optimizer):
                 o, n = self.arena.index[p._clite[1]]
                 n4 = (n + 3) // 4 * 4
                 for s in range(0, n4, CHUNK):
-                    rows.append((o + s, min(CHUNK, n4 - s), lr, wd))
+                    rows.append((o + s, min(CHUNK, n4 - s), lr, wd, self._reserved(p)))
         # frozen tensors: no work item, so the update kernel never zeroes their slice of flat_g — yet several backward kernels write
         # gradients unconditionally (BatchNorm dgamma/dbeta, LayerNorm, embeddings). Their (merged) spans are zeroed explicitly.
         spans = []
@@ -71,13 +77,17 @@ class FusedSGD(torch.optim.Optimizer):
         self._frozen_spans = [tuple(x) for x in spans]
         rows.sort()                      # by arena offset: a [lo, hi) element range of the arena is then a contiguous run of items (launch(span=...))
         arr = (hip.OptimItem * len(rows))()
-        for i, (s, c, lr, wd) in enumerate(rows):
-            arr[i].start, arr[i].count, arr[i].lr, arr[i].wd = s, c, lr, wd
+        for i, (s, c, lr, wd, tag) in enumerate(rows):
+            arr[i].start, arr[i].count, arr[i].lr, arr[i].wd, arr[i].reserved = s, c, lr, wd, tag
         host = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8)
         self._items = host.to(self.arena.device)
         self._n_items = len(rows)
         self._item_starts = [r[0] for r in rows]
         self._items_key = key
+
+    def _reserved(self, p):
+        """The `reserved` word of the items of parameter p (0: no kernel reads it)."""
+        return 0
 
     def _lr_mult(self):
         for g in self.param_groups:
@@ -141,11 +151,16 @@ class FusedSGD(torch.optim.Optimizer):
     # step() = upload_hp() + launch(). A captured hipGraph of the train step contains only launch() (and the sumsq of
     # clip_grad_norm); the host uploads this step's hyper-parameters into `hp` before every replay.
     def upload_hp(self, lookahead_sync=False, alpha=1.0, max_norm=None):
-        """Host -> device: (lr multiplier of the schedule, momentum, clip norm, Lookahead sync flag, alpha, gradient pre-scale)."""
-        mom = self.param_groups[0]["momentum"]
+        """Host -> device: (lr multiplier of the schedule, momentum / beta1, clip norm, Lookahead sync flag, alpha, gradient pre-scale), then the
+        class's own slots (_hp_tail)."""
+        g0 = self.param_groups[0]
         mn = self.max_norm if max_norm is None else float(max_norm)
-        vals = [self._lr_mult(), mom, mn, 1.0 if lookahead_sync else 0.0, alpha, self.grad_prescale, 0.0, 0.0]
-        self._upload(vals)
+        self._upload([self._lr_mult(), g0["momentum"] if "momentum" in g0 else g0["betas"][0], mn, 1.0 if lookahead_sync else 0.0, alpha,
+                      self.grad_prescale] + self._hp_tail())
+
+    def _hp_tail(self):
+        """What a class appends to the six common floats of `hp` (slots 6 ..; the rest of `hp` is zero)."""
+        return []
 
     def _upload(self, vals):
         """`vals` (padded with zeros to the length of `hp`) -> device `hp`, without a host synchronisation in the steady state."""
@@ -189,19 +204,23 @@ class FusedSGD(torch.optim.Optimizer):
         of a step and the rest at the start of the next one (train_loop.TrainStep, defer_update); every tensor exactly once per step."""
         first, n = self._launch_range(span)
         if n > 0:
-            hip.sgd_step(self.arena.flat_p, self.arena.flat_g, self.flat_v, self.flat_slow, self.arena.flat_lp,
-                         C.c_void_p(self._items.data_ptr() + first * C.sizeof(hip.OptimItem)), n, self.hp, self.sumsq)
+            self._enqueue(C.c_void_p(self._items.data_ptr() + first * C.sizeof(hip.OptimItem)), first, n)
         self.arena._tr_stale = True          # the bf16 weights changed: the transposed copies of the dgrad GEMMs are out of date
         self._dirty = False
 
-    # -- torch.optim.SGD-compatible checkpoint layout -----------------------------------------------------------------
+    def _enqueue(self, items, first, n):
+        """The class's kernels over the n items from `items` on (item `first` of the table)."""
+        raise NotImplementedError
+
+    # -- checkpoints in the layout of the torch optimizer the class mirrors: STATE's keys per parameter, plus `step` where the class counts steps ----
     def state_dict(self):
-        self.arena.flush_pending()          # a deferred share of the last update (TrainStep defer_update) must land before momentum is read
+        self.arena.flush_pending()          # a deferred share of the last update (TrainStep defer_update) must land before the state is read
         state, groups = {}, []
         for i, g in enumerate(self.param_groups):
             p = g["params"][0]
             o, n = self.arena.index[p._clite[1]]
-            state[i] = {"momentum_buffer": self.arena._torch_view(self.flat_v, o, n, p).clone()}
+            state[i] = {"step": torch.tensor(float(self.steps))} if hasattr(self, "steps") else {}
+            state[i].update((k, self.arena._torch_view(getattr(self, buf), o, n, p).clone()) for k, buf in self.STATE.items())
             groups.append({k: v for k, v in g.items() if k != "params"} | {"params": [i]})
         return {"state": state, "param_groups": groups}
 
@@ -211,13 +230,28 @@ class FusedSGD(torch.optim.Optimizer):
             saved = sd["param_groups"][i]
             for k, v in saved.items():
                 if k != "params":
-                    g[k] = v
+                    g[k] = tuple(v) if k == "betas" else v
             p = g["params"][0]
             o, n = self.arena.index[p._clite[1]]
-            st = sd["state"].get(i, sd["state"].get(str(i)))
-            if st is not None and st.get("momentum_buffer") is not None:
-                self.arena._torch_view(self.flat_v, o, n, p).copy_(st["momentum_buffer"])
+            st = sd["state"].get(i, sd["state"].get(str(i))) or {}
+            for k, buf in self.STATE.items():
+                if st.get(k) is not None:
+                    self.arena._torch_view(getattr(self, buf), o, n, p).copy_(st[k])
+            if hasattr(self, "steps") and st.get("step") is not None:
+                self.steps = int(float(st["step"]))
         self._items_key = None
+
+
+class FusedSGD(_FusedUpdate):
+    """torch.optim.SGD with momentum and weight decay, one param group per parameter (clite_sgd_step); `state_dict()` keeps its layout
+    (`momentum_buffer` per parameter)."""
+    STATE = {"momentum_buffer": "flat_v"}
+
+    def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0):
+        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, dampening=0, nesterov=False))
+
+    def _enqueue(self, items, first, n):
+        hip.sgd_step(self.arena.flat_p, self.arena.flat_g, self.flat_v, self.flat_slow, self.arena.flat_lp, items, n, self.hp, self.sumsq)
 
 
 class _PerTensorNorms:
@@ -228,25 +262,17 @@ class _PerTensorNorms:
         plist = [p for g in self.param_groups for p in g["params"]]
         adapted = [p for p in plist if p.dim() >= 2]
         self._slots = {id(p): i for i, p in enumerate(adapted)}
-        self._spans = {self.arena.index[p._clite[1]][0]: self.arena.index[p._clite[1]][1] for p in adapted}      # arena offset -> elements
         dev = self.arena.device
         self.norms = torch.zeros(max(len(adapted), 1), 2, device=dev, dtype=torch.float32)      # a pair of squared norms per adapted tensor
         n_items = sum(((self.arena.index[p._clite[1]][1] + 3) // 4 * 4 + CHUNK - 1) // CHUNK for p in plist)
         self.norm_partials = torch.zeros(2 * max(n_items, 1), device=dev, dtype=torch.float32)  # the reduction's first stage: a pair per item
 
-    def _build_items(self):
-        """The base class's table, then the `reserved` word of every item of an adapted tensor: that tensor's norm slot + 1."""
-        if self._base_lrs() == self._items_key:
-            return
-        super()._build_items()
-        owners = sorted((self.arena.index[p._clite[1]][0], self._slots[id(p)] + 1) for g in self.param_groups for p in g["params"] if id(p) in self._slots)
-        offs = [o for o, _ in owners]
-        arr = (hip.OptimItem * self._n_items).from_buffer_copy(self._items.cpu().numpy().tobytes())
-        for i, start in enumerate(self._item_starts):          # items never straddle tensors: the owner is the last tensor starting at or before the item
-            k = bisect.bisect_right(offs, start) - 1
-            if k >= 0 and start < offs[k] + self._spans[owners[k][0]]:
-                arr[i].reserved = owners[k][1]
-        self._items = torch.frombuffer(bytearray(bytes(arr)), dtype=torch.uint8).to(self.arena.device)
+    def _reserved(self, p):
+        return self._slots.get(id(p), -1) + 1
+
+    def _partials(self, first, n):
+        """Every span has its own share of the partials: two spans may be in flight on two streams (TrainStep: update_img / update_rest)."""
+        return self.norm_partials[2 * first:2 * (first + n)]
 
     def tensor_norms(self, p):
         """The two norms of an adapted parameter as the last launch that updated it measured them."""
@@ -261,111 +287,45 @@ class FusedLARS(_PerTensorNorms, FusedSGD):
     normalisation scales (ndim <= 1) move exactly as under FusedSGD. The per-tensor norms are two launches over the item table
     (clite_lars_norms: fixed order, no float atomics), the update one (clite_lars_step); launch(span) takes the norms of the span it updates.
     tensor_norms(p) is (|p|, |g|), of the raw gradient: before pre-scale and clipping."""
+    HP_LEN = 8          # FusedSGD's six, [6] the trust coefficient, [7] eps
 
     def __init__(self, params, lr=1e-3, momentum=0.0, weight_decay=0.0, trust_coefficient=0.001, eps=1e-8):
         super().__init__(params, lr=lr, momentum=momentum, weight_decay=weight_decay)
         self.trust_coefficient, self.eps = float(trust_coefficient), float(eps)
         self._init_norms()
 
-    def upload_hp(self, lookahead_sync=False, alpha=1.0, max_norm=None):
-        """FusedSGD.upload_hp with the trust coefficient and eps in slots 6 and 7."""
-        mom = self.param_groups[0]["momentum"]
-        mn = self.max_norm if max_norm is None else float(max_norm)
-        vals = [self._lr_mult(), mom, mn, 1.0 if lookahead_sync else 0.0, alpha, self.grad_prescale, self.trust_coefficient, self.eps]
-        self._upload(vals)
+    def _hp_tail(self):
+        return [self.trust_coefficient, self.eps]
 
-    @torch.no_grad()
-    def launch(self, span=None):
-        first, n = self._launch_range(span)
-        if n > 0:
-            items = C.c_void_p(self._items.data_ptr() + first * C.sizeof(hip.OptimItem))
-            # every span has its own share of the partials: two spans may be in flight on two streams (TrainStep: update_img / update_rest)
-            hip.lars_norms(self.arena.flat_p, self.arena.flat_g, items, n, self.norm_partials[2 * first:2 * (first + n)], self.norms)
-            hip.lars_step(self.arena.flat_p, self.arena.flat_g, self.flat_v, self.flat_slow, self.arena.flat_lp, items, n, self.hp, self.sumsq,
-                          self.norms)
-        self.arena._tr_stale = True
-        self._dirty = False
+    def _enqueue(self, items, first, n):
+        A = self.arena
+        hip.lars_norms(A.flat_p, A.flat_g, items, n, self._partials(first, n), self.norms)
+        hip.lars_step(A.flat_p, A.flat_g, self.flat_v, self.flat_slow, A.flat_lp, items, n, self.hp, self.sumsq, self.norms)
 
 
-class FusedAdamW(FusedSGD):
+class FusedAdamW(_FusedUpdate):
     """torch.optim.AdamW (reference factories.py:439, `OPTIM.OPTIMIZER_NAME: adamw`, torch's default betas / eps) on the same arena, work items, clipping,
     Lookahead hook and captured-step protocol as FusedSGD (clite_adamw_step). `state_dict()` keeps torch.optim.AdamW's layout (step, exp_avg, exp_avg_sq
     per parameter). The step count - the bias corrections' exponent - advances once per upload_hp(), i.e. once per optimizer step however many span
     launches the captured step splits it into."""
+    HP_LEN = 12
+    STATE = {"exp_avg": "flat_v", "exp_avg_sq": "flat_v2"}
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2):
-        torch.optim.Optimizer.__init__(self, params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
-        plist = [p for g in self.param_groups for p in g["params"]]
-        arenas = {id(p._clite[0]) for p in plist if hasattr(p, "_clite")}
-        if len(arenas) != 1 or any(not hasattr(p, "_clite") for p in plist):
-            raise RuntimeError("FusedAdamW: parameters must live in one device arena - move the model to the GPU (model.to(device)) before building the "
-                               "optimizer, as reference train.py:136-138 does")
-        self.arena = plist[0]._clite[0]
-        dev = self.arena.device
-        self.flat_v = torch.zeros(self.arena.total, device=dev, dtype=torch.float32)           # exp_avg
-        self.flat_v2 = torch.zeros(self.arena.total, device=dev, dtype=torch.float32)          # exp_avg_sq
-        self.flat_slow = self.arena.flat_p.clone()
-        self.hp = torch.zeros(12, device=dev, dtype=torch.float32)
-        self.sumsq = torch.zeros(1, device=dev, dtype=torch.float32)
-        self.sumsq_partials = torch.zeros(1024, device=dev, dtype=torch.float32)
-        self.max_norm = 0.0
-        self.grad_prescale = 1.0
-        self._items = None
-        self._hp_ring = None
-        self._items_key = None
-        self.before_step = None
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay))
         self.steps = 0
 
     def upload_hp(self, lookahead_sync=False, alpha=1.0, max_norm=None):
         self.steps += 1
-        b1, b2 = self.param_groups[0]["betas"]
-        mn = self.max_norm if max_norm is None else float(max_norm)
-        vals = [self._lr_mult(), b1, mn, 1.0 if lookahead_sync else 0.0, alpha, self.grad_prescale, b2, self.param_groups[0]["eps"],
-                1.0 - b1 ** self.steps, 1.0 - b2 ** self.steps, 1.0 - b1, 1.0 - b2] + self._hp_tail()
-        self._upload(vals)
+        super().upload_hp(lookahead_sync, alpha, max_norm)
 
     def _hp_tail(self):
-        """What a subclass appends to the twelve floats of `hp`."""
-        return []
+        """[6] beta2, [7] eps, [8] 1 - beta1^t, [9] 1 - beta2^t, [10] 1 - beta1, [11] 1 - beta2, formed in double as torch does."""
+        b1, b2 = self.param_groups[0]["betas"]
+        return [b2, self.param_groups[0]["eps"], 1.0 - b1 ** self.steps, 1.0 - b2 ** self.steps, 1.0 - b1, 1.0 - b2]
 
-    @torch.no_grad()
-    def launch(self, span=None):
-        first, n = self._launch_range(span)
-        if n > 0:
-            hip.adamw_step(self.arena.flat_p, self.arena.flat_g, self.flat_v, self.flat_v2, self.flat_slow, self.arena.flat_lp,
-                           C.c_void_p(self._items.data_ptr() + first * C.sizeof(hip.OptimItem)), n, self.hp, self.sumsq)
-        self.arena._tr_stale = True
-        self._dirty = False
-
-    def state_dict(self):
-        self.arena.flush_pending()
-        state, groups = {}, []
-        for i, g in enumerate(self.param_groups):
-            p = g["params"][0]
-            o, n = self.arena.index[p._clite[1]]
-            state[i] = {"step": torch.tensor(float(self.steps)), "exp_avg": self.arena._torch_view(self.flat_v, o, n, p).clone(),
-                        "exp_avg_sq": self.arena._torch_view(self.flat_v2, o, n, p).clone()}
-            groups.append({k: v for k, v in g.items() if k != "params"} | {"params": [i]})
-        return {"state": state, "param_groups": groups}
-
-    def load_state_dict(self, sd):
-        self.arena.flush_pending()
-        for i, g in enumerate(self.param_groups):
-            saved = sd["param_groups"][i]
-            for k, v in saved.items():
-                if k != "params":
-                    g[k] = tuple(v) if k == "betas" else v
-            p = g["params"][0]
-            o, n = self.arena.index[p._clite[1]]
-            st = sd["state"].get(i, sd["state"].get(str(i)))
-            if st is not None:
-                if st.get("exp_avg") is not None:
-                    self.arena._torch_view(self.flat_v, o, n, p).copy_(st["exp_avg"])
-                if st.get("exp_avg_sq") is not None:
-                    self.arena._torch_view(self.flat_v2, o, n, p).copy_(st["exp_avg_sq"])
-                if st.get("step") is not None:
-                    self.steps = int(float(st["step"]))
-        self._items_key = None
+    def _enqueue(self, items, first, n):
+        hip.adamw_step(self.arena.flat_p, self.arena.flat_g, self.flat_v, self.flat_v2, self.flat_slow, self.arena.flat_lp, items, n, self.hp, self.sumsq)
 
 
 class FusedLAMB(_PerTensorNorms, FusedAdamW):
@@ -375,15 +335,15 @@ class FusedLAMB(_PerTensorNorms, FusedAdamW):
     is zero; capped at 1 with trust_clip), biases and normalisation scales (ndim <= 1) exactly as under FusedAdamW. Bias correction is always on;
     there is no eps in q and no trust coefficient. Two launches per span: clite_lamb_moments (moments in place, the per-tensor norms in a fixed
     order, no float atomics) and clite_lamb_step. tensor_norms(p) is (|p| before the update, |r|)."""
+    HP_LEN = 16          # FusedAdamW's twelve, [12] the TRUST_CLIP flag
 
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, trust_clip=False):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay)
         self.trust_clip = bool(trust_clip)
-        self.hp = torch.zeros(16, device=self.arena.device, dtype=torch.float32)          # FusedAdamW's twelve, [12] the TRUST_CLIP flag
         self._init_norms()
 
     def _hp_tail(self):
-        return [1.0 if self.trust_clip else 0.0]
+        return super()._hp_tail() + [1.0 if self.trust_clip else 0.0]
 
     def trust_ratio(self, p):
         """q of an adapted parameter in the last launch that updated it."""
@@ -391,18 +351,10 @@ class FusedLAMB(_PerTensorNorms, FusedAdamW):
         q = pn / rn if pn > 0 and rn > 0 else 1.0
         return min(q, 1.0) if self.trust_clip else q
 
-    @torch.no_grad()
-    def launch(self, span=None):
-        first, n = self._launch_range(span)
-        if n > 0:
-            items = C.c_void_p(self._items.data_ptr() + first * C.sizeof(hip.OptimItem))
-            A = self.arena
-            # every span has its own share of the partials: two spans may be in flight on two streams (TrainStep: update_img / update_rest)
-            hip.lamb_moments(A.flat_p, A.flat_g, self.flat_v, self.flat_v2, items, n, self.hp, self.sumsq, self.norm_partials[2 * first:2 * (first + n)],
-                             self.norms)
-            hip.lamb_step(A.flat_p, A.flat_g, self.flat_v, self.flat_v2, self.flat_slow, A.flat_lp, items, n, self.hp, self.sumsq, self.norms)
-        self.arena._tr_stale = True
-        self._dirty = False
+    def _enqueue(self, items, first, n):
+        A = self.arena
+        hip.lamb_moments(A.flat_p, A.flat_g, self.flat_v, self.flat_v2, items, n, self.hp, self.sumsq, self._partials(first, n), self.norms)
+        hip.lamb_step(A.flat_p, A.flat_g, self.flat_v, self.flat_v2, self.flat_slow, A.flat_lp, items, n, self.hp, self.sumsq, self.norms)
 
 
 class Lookahead(object):

@@ -1,4 +1,4 @@
-"""Float64 reference of the LAMB update (csrc/lamb_ops.hip, optim.FusedLAMB; You et al. 2020, Algorithm 2), evaluated on the stored f32 inputs and
+"""Float64 reference of the LAMB update (csrc/update_ops.hip, optim.FusedLAMB; You et al. 2020, Algorithm 2), evaluated on the stored f32 inputs and
 the f32 hyper-parameters the kernel reads. Nothing here calls into clip_lite_amd. For every tensor t (loss_ref.adamw_step_ref's names):
 
     g' = g * gs * clip                               clip from the global sumsq, as loss_ref.clip_factor
@@ -14,10 +14,11 @@ from collections import namedtuple
 
 import numpy as np
 
-import lars_ref as L
 import loss_ref as R
-from lars_ref import CHUNK, N_SLOTS, SENT, TABLE, Tensor, clip_setup, f32  # noqa: F401
+import update_table as U
+from lars_ref import f32  # noqa: F401
 from loss_ref import clip_factor
+from update_table import CHUNK, N_SLOTS, OPTIONS, SENT, TABLE, Tensor, clip_setup, kept as _kept  # noqa: F401
 
 Step = namedtuple("Step", "p m v2 slow q r")               # q, r: per element (q = 1 and r = 0 outside every tensor)
 
@@ -66,7 +67,7 @@ def lamb_step_ref(p, g, m, v2, slow, lr, wd, max_norm, sync, alpha, gs, b2, eps,
 # copies of the buffers: ("moments" | "lamb" | "adamw", first item, number of items). A moments call gets partials[2 first : 2 (first + n)], as
 # FusedLAMB.launch passes them. tests/test_wavesim_lamb.py runs the kernels on the wave simulator, tests/test_gpu_lamb_ops.py on the device.
 #
-# The item table is lars_ref.table(): tensors of 4 (thread 0 alone), 1028 (second sweep), 8192 (exactly one item) and 8192 * 3 + 1020 elements (four
+# The item table is update_table.table(): tensors of 4 (thread 0 alone), 1028 (second sweep), 8192 (exactly one item) and 8192 * 3 + 1020 elements (four
 # items, ragged last), two not-adapted tensors between adapted ones, an adapted tensor with g = 0, zero moments and wd = 0 (r = 0, so q = 1: its
 # weight decay is the one figure changed against lars_ref's table) and one with p = 0 (q = 1; it still moves by lr u). Sentinels in every gap,
 # behind every buffer, in the norm slots no tensor owns and in the partial pairs of not-adapted items. The adapted tensors' parameters are
@@ -77,13 +78,12 @@ MEASURED = {}                                  # running maxima of what the chec
 
 
 def _note(name, value):
-    MEASURED[name] = max(MEASURED.get(name, 0.0), float(value))
-    return MEASURED[name]
+    return U.note(MEASURED, name, value)
 
 
 def table(adapt=True):
-    """lars_ref.table() with the weight decay of the g = 0 tensor set to 0."""
-    rows, tensors, slots, heads, n = L.table(adapt)
+    """update_table.table() with the weight decay of the g = 0 tensor set to 0."""
+    rows, tensors, slots, heads, n = U.table(adapt)
     for t, (_, _, special) in zip(tensors, TABLE):
         if special == "g0":
             rows = [(s, c, lr, 0.0 if t.start <= s < t.start + t.n else wd, tag) for s, c, lr, wd, tag in rows]
@@ -94,9 +94,7 @@ def problem(seed, adapt=True, step=1000):
     """step 1: the zero moments FusedLAMB starts from; a later step: random m and v2 >= m^2, as test_gpu_optim_ops.test_adamw_step_matches_float64."""
     rows, tensors, slots, heads, n = table(adapt)
     rng = np.random.default_rng(seed)
-    inside = np.zeros(n, bool)
-    for t in tensors:
-        inside[t.start:t.start + t.n] = True
+    inside = U.inside_of(tensors, n)
     p, g, slow = (np.where(inside, rng.standard_normal(n), SENT).astype(np.float32) for _ in range(3))
     g = np.where(inside, g * 0.01, SENT).astype(np.float32)
     if step == 1:
@@ -111,11 +109,7 @@ def problem(seed, adapt=True, step=1000):
             g[s] = m[s] = v2[s] = 0.0
         if special == "p0":
             p[s] = 0.0
-    bufs = {"p": p, "g": g, "m": m, "v2": v2, "slow": slow, "cast": R.to_bf16_bits(np.full(n, 3.0, np.float32)),
-            "partials": np.full(2 * len(rows) + 8, SENT, np.float32), "norms": np.full(2 * N_SLOTS + 8, SENT, np.float32)}
-    lr, wd = np.zeros(n), np.zeros(n)
-    for s, c, a, b, _ in rows:
-        lr[s:s + c], wd[s:s + c] = np.float32(a), np.float32(b)
+    bufs, lr, wd = U.finish_problem({"p": p, "g": g, "m": m, "v2": v2, "slow": slow}, rows, n)
     return bufs, rows, tensors, slots, heads, inside, lr, wd
 
 
@@ -131,31 +125,9 @@ def _ref(bufs, lr, wd, hp, ss, tensors):
                          h[10], h[11], float(ss), h[12] != 0, tensors)
 
 
-def _kept(name, got, before, keep):
-    assert R.same_bits(np.ascontiguousarray(got[keep]), np.ascontiguousarray(before[keep])), f"{name}: a kept element changed"
-
-
 def _check_norms_of(what, out, bufs, ref, tensors, slots, launched):
     """norms after a moments call over the tensors `launched` (indices): the launched slots against float64, every other slot untouched."""
-    norms = out["norms"]
-    want = squared_norms(bufs["p"], ref.r, tensors)
-    live = set()
-    for i in launched:
-        if slots[i] is None:
-            continue
-        live.add(slots[i])
-        t = tensors[i]
-        for k, (name, arr) in enumerate((("p", bufs["p"]), ("r", ref.r))):
-            terms = np.asarray(arr[t.start:t.start + t.n], np.float64) ** 2
-            den = max(1.0, terms.sum())
-            err = abs(float(norms[2 * slots[i] + k]) - want[i][k]) / den
-            print(f"LAMBERR {what} norms: tensor {i} ({t.n} elements) sum {name}^2: error / max(1, sum terms) = {err:.2e}, "
-                  f"running max {_note('norms', err):.2e} (bound 1e-5)")
-            assert err <= 1e-5, (what, i, name, err)
-    dead = np.ones(len(norms), bool)
-    for s in live:
-        dead[2 * s:2 * s + 2] = False
-    assert (norms[dead] == SENT).all(), f"{what}: a slot of a tensor outside the launched range (or behind the buffer) was written"
+    U.check_norm_slots("LAMBERR", what, out["norms"], (("p", bufs["p"]), ("r", ref.r)), tensors, slots, launched, MEASURED)
 
 
 def _check_moments(what, out, ref, inside):
@@ -205,10 +177,6 @@ def check_norms(be, step):
     for name in ("m", "v2"):
         _kept(name + " of the tensors not launched", sub[name], bufs[name], before)
         assert R.same_bits(sub[name][~before], out[name][~before])
-
-
-# (sync, cast given, clipping, pre-scale): every option in both states, not the full product (tests/test_gpu_optim_ops.py, tests/lars_ref.py)
-OPTIONS = L.OPTIONS
 
 
 def check_step(be, sync, cast, clip, gs, step, trust_clip):

@@ -1,4 +1,4 @@
-"""Float64 reference of the LARS update (csrc/lars_ops.hip, optim.FusedLARS), evaluated on the stored f32 inputs and the f32 hyper-parameters the
+"""Float64 reference of the LARS update (csrc/update_ops.hip, optim.FusedLARS), evaluated on the stored f32 inputs and the f32 hyper-parameters the
 kernel reads. Nothing here calls into clip_lite_amd. For every tensor t (loss_ref.sgd_step_ref's names):
 
     g' = g * gs * clip                               clip from the global sumsq, as loss_ref.clip_factor
@@ -13,9 +13,11 @@ from collections import namedtuple
 
 import numpy as np
 
+import loss_ref as R
+import update_table as U
 from loss_ref import clip_factor
+from update_table import CHUNK, N_SLOTS, OPTIONS, SENT, TABLE, Tensor, clip_setup, kept as _kept, table  # noqa: F401
 
-Tensor = namedtuple("Tensor", "start n adapted")          # a tensor's element range [start, start + n) of the flat buffers
 Step = namedtuple("Step", "p v slow q u")                  # q, u: per element (q = 1 and u = 0 outside every tensor)
 
 
@@ -61,100 +63,36 @@ def lars_step_ref(p, g, v, slow, lr, wd, mu, max_norm, sync, alpha, gs, sumsq, e
 # bits, or None: no bf16 copy is given to the kernel), partials, norms (f32); rows: [(start, count, lr, wd, reserved)]; calls, run in order on copies
 # of the buffers: ("norms" | "lars" | "sgd", first item, number of items). A norms call gets partials[2 first : 2 (first + n)], as FusedLARS.launch
 # passes them. tests/test_wavesim_lars.py runs the kernels on the wave simulator, tests/test_gpu_lars_ops.py on the device.
-import loss_ref as R  # noqa: E402
-
-SENT = 100.0
-CHUNK = 8192                                   # the host's elements per item (optim/fused_sgd.py)
-PAIRS = [(0.2, 1e-4), (1e-3, 0.0), (0.05, 5e-2)]          # (lr, wd) of tensor i: PAIRS[i % 3]
-# (elements, norm slot or None = not adapted, special). One workgroup per item, a sweep is 256 threads x 4 elements: 4 -> thread 0 alone; 1028 ->
-# thread 0 takes a second sweep; 8192 -> exactly one item; 8192 * 3 + 1020 -> four items, the last one ragged (255 threads); two not-adapted
-# tensors between adapted ones (reserved = 0: they must never read norms); an adapted tensor with g = 0 and one with p = 0 (q = 1). The slots are
-# deliberately not in table order, and slots 4 and 7 belong to no tensor.
-TABLE = [(4, 5, None), (64, None, None), (1028, 0, None), (8192, 3, None), (1020, None, None), (8192 * 3 + 1020, 1, None), (260, 6, "g0"),
-         (516, 2, "p0")]
-N_SLOTS = 8
+# The item table is update_table.table().
 ETA, EPS = 1.0, 1e-8                           # eta = 1: q u is of order one (at eta = 0.001 a wrong ratio hides under the SGD bound)
 MEASURED = {}                                  # running maxima of what the checks print, by name
 
 
 def _note(name, value):
-    MEASURED[name] = max(MEASURED.get(name, 0.0), float(value))
-    return MEASURED[name]
-
-
-def table(adapt=True):
-    """rows, [Tensor], [slot or None], [index of each tensor's first item], arena length. Starts are multiples of 64; a gap of >= 64 sentinel
-    elements precedes the first tensor and follows every tensor. adapt = False: the same table with every reserved word 0."""
-    rows, tensors, slots, heads, start = [], [], [], [], 64
-    for i, (n, slot, _) in enumerate(TABLE):
-        lr, wd = PAIRS[i % 3]
-        if not adapt:
-            slot = None
-        tensors.append(Tensor(start, n, slot is not None))
-        slots.append(slot)
-        heads.append(len(rows))
-        for s in range(0, n, CHUNK):
-            rows.append((start + s, min(CHUNK, n - s), lr, wd, 0 if slot is None else slot + 1))
-        start = (start + n + 63) // 64 * 64 + 64
-    return rows, tensors, slots, heads, start
+    return U.note(MEASURED, name, value)
 
 
 def problem(seed, adapt=True):
     rows, tensors, slots, heads, n = table(adapt)
     rng = np.random.default_rng(seed)
-    inside = np.zeros(n, bool)
-    for t in tensors:
-        inside[t.start:t.start + t.n] = True
+    inside = U.inside_of(tensors, n)
     p, g, v, slow = (np.where(inside, rng.standard_normal(n), SENT).astype(np.float32) for _ in range(4))
     for t, (_, _, special) in zip(tensors, TABLE):
         if special == "g0":
             g[t.start:t.start + t.n] = 0.0
         if special == "p0":
             p[t.start:t.start + t.n] = 0.0
-    bufs = {"p": p, "g": g, "v": v, "slow": slow, "cast": R.to_bf16_bits(np.full(n, 3.0, np.float32)),
-            "partials": np.full(2 * len(rows) + 8, SENT, np.float32), "norms": np.full(2 * N_SLOTS + 8, SENT, np.float32)}
-    lr, wd = np.zeros(n), np.zeros(n)
-    for s, c, a, b, _ in rows:
-        lr[s:s + c], wd[s:s + c] = np.float32(a), np.float32(b)
+    bufs, lr, wd = U.finish_problem({"p": p, "g": g, "v": v, "slow": slow}, rows, n)
     return bufs, rows, tensors, slots, heads, inside, lr, wd
-
-
-def clip_setup(clip, g, inside, gs):
-    """(max_norm, sumsq value): clipping active (norm = 2 max_norm), inactive (norm = max_norm / 2), or disabled with NaN in sumsq."""
-    ss = np.float32((g[inside].astype(np.float64) ** 2).sum())
-    norm = float(np.sqrt(ss)) * gs
-    return {"active": (norm / 2, ss), "inactive": (norm * 2, ss), "disabled": (0.0, np.float32("nan"))}[clip]
 
 
 def _hp(max_norm=0.0, sync=False, gs=1.0):
     return np.array([0.5, 0.9, max_norm, float(sync), 0.5, gs, ETA, EPS], np.float32)
 
 
-def _kept(name, got, before, keep):
-    assert R.same_bits(np.ascontiguousarray(got[keep]), np.ascontiguousarray(before[keep])), f"{name}: a kept element changed"
-
-
 def _check_norms_of(what, out, bufs, tensors, slots, launched):
     """norms / partials after a norms call over the tensors `launched` (indices): the launched slots against float64, every other slot untouched."""
-    norms = out["norms"]
-    ref = squared_norms(bufs["p"], bufs["g"], tensors)
-    live = set()
-    for i in launched:
-        if slots[i] is None:
-            continue
-        live.add(slots[i])
-        t = tensors[i]
-        for k, name in enumerate(("p", "g")):
-            terms = bufs[name][t.start:t.start + t.n].astype(np.float64) ** 2
-            den = max(1.0, terms.sum())
-            err = abs(float(norms[2 * slots[i] + k]) - ref[i][k]) / den
-            print(f"LARSERR {what} norms: tensor {i} ({t.n} elements) sum {name}^2: error / max(1, sum terms) = {err:.2e}, "
-                  f"running max {_note('norms', err):.2e} (bound 1e-5)")
-            assert err <= 1e-5, (what, i, name, err)
-    dead = np.ones(len(norms), bool)
-    for s in live:
-        dead[2 * s:2 * s + 2] = False
-    assert (norms[dead] == SENT).all(), f"{what}: a slot of a tensor outside the launched range (or behind the buffer) was written"
+    U.check_norm_slots("LARSERR", what, out["norms"], (("p", bufs["p"]), ("g", bufs["g"])), tensors, slots, launched, MEASURED)
 
 
 def check_norms(be):
@@ -181,11 +119,6 @@ def check_norms(be):
         if slots[i] is not None:
             assert R.same_bits(sub["norms"][2 * slots[i]:2 * slots[i] + 2], out["norms"][2 * slots[i]:2 * slots[i] + 2]), i
     assert (sub["partials"][:2 * k] == SENT).all()
-
-
-# (sync, cast given, clipping, pre-scale): every option in both states, not the full product
-OPTIONS = [(False, True, "active", 0.25), (True, False, "inactive", 1.0), (True, True, "disabled", 0.25), (False, False, "disabled", 1.0),
-           (True, True, "active", 1.0)]
 
 
 def check_step(be, sync, cast, clip, gs):

@@ -1,4 +1,4 @@
-"""float64 references of the loss, cross-entropy and parameter-update kernels (csrc/loss_ops.hip, csrc/cls_ops.hip, csrc/optim_ops.hip), written
+"""float64 references of the loss, cross-entropy and parameter-update kernels (csrc/loss_ops.hip, csrc/cls_ops.hip, csrc/optim_ops.hip, csrc/update_ops.hip), written
 from the operations' definitions on plain numpy / torch-CPU float64 (gradients from torch.autograd). Nothing here calls into clip_lite_amd or the
 wave simulator. Every function takes the STORAGE-ROUNDED inputs (a bf16 input is rounded before it gets here, as in tests/resnet_ref.py) and
 returns every output of the kernel, all float64 numpy. tests/test_loss_ref_host.py checks every gradient against central finite differences.
@@ -210,7 +210,7 @@ def sgd_step_ref(p, g, v, slow, lr, wd, mu, max_norm, sync, alpha, gs, sumsq):
 
 
 def adamw_step_ref(p, g, m, v2, slow, lr, wd, max_norm, sync, alpha, gs, b2, eps, bc1, bc2, omb1, omb2, sumsq):
-    """torch.optim.AdamW's step as csrc/optim_ops.hip states it: decoupled decay, exp_avg.lerp_, bias-corrected moments, then the Lookahead sync."""
+    """torch.optim.AdamW's step as csrc/update_ops.hip states it: decoupled decay, exp_avg.lerp_, bias-corrected moments, then the Lookahead sync."""
     p, g, m, v2, slow = (np.asarray(a, np.float64) for a in (p, g, m, v2, slow))
     ge = g * (gs * clip_factor(sumsq, gs, max_norm))
     p = p * (1 - lr * wd)

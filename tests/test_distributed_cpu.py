@@ -156,7 +156,7 @@ def _dp_worker(rank, world, port, tmp):
     from clip_lite_amd.runtime import Arena
     from clip_lite_amd.utils import distributed as D
     simlib.build_sim()
-    hip._lib, hip._allow_host_tensors = hip._bind(C.CDLL(simlib.SIM_SO)), True      # the same csrc/optim_ops.hip, compiled for the host
+    hip._lib, hip._allow_host_tensors = hip._bind(C.CDLL(simlib.SIM_SO)), True      # the same csrc/update_ops.hip, compiled for the host
     net = _tiny_net()
     if rank == 1:                                   # rank 1 starts from different parameters: the broadcast must repair that
         with torch.no_grad():

@@ -1,4 +1,4 @@
-"""FusedLAMB on the GPU, host level (optim/fused_sgd.py over csrc/lamb_ops.hip): tests/test_gpu_lars.py's small arena of hand-picked tensors with
+"""FusedLAMB on the GPU, host level (optim/fused_sgd.py over csrc/update_ops.hip): tests/test_gpu_lars.py's small arena of hand-picked tensors with
 random fixed gradients against the float64 reference (tests/lamb_ref.py) through Lookahead, clipping, the checkpoint layout, span launches and the
 factory; then configs/smoke_random_lamb.yaml through TrainStep, eager and captured. The step bounds are those of tests/test_gpu_lamb_ops.py: p and
 slow per element within 2e-6 * max(1, max|ref|) + 2e-5 * |delta_ref|, delta_ref = lr q r, the moments within 1e-5 * max|ref|, every step's

@@ -1,4 +1,4 @@
-"""Kernel-level GPU checks of the LAMB kernels (csrc/lamb_ops.hip) through clip_lite_amd.hip: lamb_moments and lamb_step called directly with the
+"""Kernel-level GPU checks of the LAMB kernels (csrc/update_ops.hip) through clip_lite_amd.hip: lamb_moments and lamb_step called directly with the
 hand-made OptimItem table of tests/lamb_ref.py (the checks are shared with tests/test_wavesim_lamb.py). Reference: lamb_ref.lamb_step_ref, float64
 on the stored f32 inputs and the f32 hyper-parameters the kernel reads, fed the float64 norms.
 

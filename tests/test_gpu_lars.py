@@ -1,4 +1,4 @@
-"""FusedLARS on the GPU, host level (optim/fused_sgd.py over csrc/lars_ops.hip): a small arena of hand-picked tensors with random fixed gradients
+"""FusedLARS on the GPU, host level (optim/fused_sgd.py over csrc/update_ops.hip): a small arena of hand-picked tensors with random fixed gradients
 against the float64 reference (tests/lars_ref.py) through Lookahead, clipping, the checkpoint layout and the factory; then
 configs/smoke_random_lars.yaml through TrainStep, eager and captured. The step bounds are those of tests/test_gpu_lars_ops.py: per element
 1e-6 * max(1, |ref|) + 2e-5 * |delta_ref|, every step's reference evaluated on the f32 state the device held before that step; the norms' bound is

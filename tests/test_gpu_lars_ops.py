@@ -1,4 +1,4 @@
-"""Kernel-level GPU checks of the LARS kernels (csrc/lars_ops.hip) through clip_lite_amd.hip: lars_norms and lars_step called directly with the
+"""Kernel-level GPU checks of the LARS kernels (csrc/update_ops.hip) through clip_lite_amd.hip: lars_norms and lars_step called directly with the
 hand-made OptimItem table of tests/lars_ref.py (the checks are shared with tests/test_wavesim_lars.py). Reference: lars_ref.lars_step_ref, float64
 on the stored f32 inputs and the f32 hyper-parameters the kernel reads, fed the float64 norms. eta = 1, so that q u is of order one.
 

@@ -1,4 +1,4 @@
-"""Kernel-level GPU checks of the parameter-update kernels (csrc/optim_ops.hip) through clip_lite_amd.hip: sumsq, sgd_step and adamw_step called
+"""Kernel-level GPU checks of the parameter-update kernels (csrc/update_ops.hip, csrc/optim_ops.hip) through clip_lite_amd.hip: sumsq, sgd_step and adamw_step called
 directly with a hand-made OptimItem table, cast_bf16, transpose_weights with a five-item table, sum_slices. References: tests/loss_ref.py
 (float64 on the stored f32 inputs and the f32 hyper-parameters the kernel reads).
 
@@ -8,7 +8,7 @@ torch.optim.AdamW); the bf16 copy equals the round-to-nearest-even of the RETURN
 items, every tail and every buffer the options switch off come back bit for bit; cast_bf16, transpose_weights, sum_slices: exact. No bound was
 replaced through the float32 procedure.
 
-Which device path the shapes take (from the launchers in csrc/optim_ops.hip):
+Which device path the shapes take (from the launchers in csrc/update_ops.hip and csrc/optim_ops.hip):
   sumsq 0 / 3 / 5        one workgroup; no 4-element chunk (0, 3: the tail loop of thread 0 alone) | one chunk and a 1-element tail
   sumsq 1027             256 chunks: one full workgroup, 3-element tail; out += over one partial
   sumsq 1048583          262145 chunks ask for 1025 workgroups, the cap of 1024 gives thread 0 of workgroup 0 a second trip; 3-element tail; the
@@ -38,6 +38,7 @@ import pytest
 import torch
 
 import loss_ref as R
+from update_table import OPTIONS, clip_setup as _clip_setup
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -114,18 +115,6 @@ def _per_element(rows, n):
     for s, c, a, b in rows:
         lr[s:s + c], wd[s:s + c] = np.float32(a), np.float32(b)
     return lr, wd
-
-
-def _clip_setup(clip, g, inside, gs):
-    """(max_norm, sumsq value): clipping active (norm = 2 max_norm), inactive (norm = max_norm / 2), or disabled with NaN in sumsq."""
-    ss = np.float32((g[inside].astype(np.float64) ** 2).sum())
-    norm = float(np.sqrt(ss)) * gs
-    return {"active": (norm / 2, ss), "inactive": (norm * 2, ss), "disabled": (0.0, np.float32("nan"))}[clip]
-
-
-# (sync, cast given, clipping, pre-scale): every option in both states, not the full product
-OPTIONS = [(False, True, "active", 0.25), (True, False, "inactive", 1.0), (True, True, "disabled", 0.25), (False, False, "disabled", 1.0),
-           (True, True, "active", 1.0)]
 
 
 def _check_untouched(name, t, before, keep):

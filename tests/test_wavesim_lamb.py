@@ -1,4 +1,4 @@
-"""The LAMB kernels (csrc/lamb_ops.hip: clite_lamb_moments, clite_lamb_step) on the wave simulator, with the checks of tests/test_gpu_lamb_ops.py
+"""The LAMB kernels (csrc/update_ops.hip: clite_lamb_moments, clite_lamb_step) on the wave simulator, with the checks of tests/test_gpu_lamb_ops.py
 (tests/lamb_ref.py: the hand-made item table, the float64 reference, the bounds). Runs without a GPU.
 
 Measured on the simulator (`pytest -s`, LAMBERR lines; maxima over the file's cases; no figure feeds a bound):

@@ -1,4 +1,4 @@
-"""The LARS kernels (csrc/lars_ops.hip: clite_lars_norms, clite_lars_step) on the wave simulator, with the checks of tests/test_gpu_lars_ops.py
+"""The LARS kernels (csrc/update_ops.hip: clite_lars_norms, clite_lars_step) on the wave simulator, with the checks of tests/test_gpu_lars_ops.py
 (tests/lars_ref.py: the hand-made item table, the float64 reference, the bounds). Runs without a GPU."""
 import ctypes as C
 
