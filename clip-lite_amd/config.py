@@ -133,6 +133,8 @@ class Config(object):
         _C.MODEL.VISUAL.FEATURE_SIZE = 2048
         _C.MODEL.VISUAL.FROZEN = False
         _C.MODEL.VISUAL.SELF_SUPERVISED = False
+        # ViT towers only: the share of patch tokens each image drops in training (FLIP patch dropout, vit.kept_patches); 0 = off
+        _C.MODEL.VISUAL.PATCH_DROPOUT = 0.0
         _C.MODEL.TEXTUAL = Node()
         _C.MODEL.TEXTUAL.NAME = "train_sbert"
         _C.MODEL.TEXTUAL.PRETRAINED = False

@@ -63,6 +63,7 @@ template <> struct Raw8<bf16> {
   u32x4 a;
   DEV void ld(const bf16* p) { a = *(const u32x4*)p; }
   DEV void ldb(rsrc_t r, uint32_t byte_off) { a = buf_load16(r, byte_off); }          // branch-free form: out-of-range offset -> zeros
+  DEV void stb(rsrc_t r, uint32_t byte_off) const { buf_store16(r, byte_off, a); }   // a copy of the 8 elements as loaded; out-of-range offset -> dropped
   DEV void get(float (&v)[8]) const {
     Chunk16 c;
     c.u = a;
@@ -78,6 +79,12 @@ template <> struct Raw8<float> {
     x.u = buf_load16(r, byte_off);
     y.u = buf_load16(r, byte_off == OOB_OFF ? OOB_OFF : byte_off + 16);
     a = x.f; b = y.f;
+  }
+  DEV void stb(rsrc_t r, uint32_t byte_off) const {
+    union { u32x4 u; f32x4 f; } x, y;
+    x.f = a; y.f = b;
+    buf_store16(r, byte_off, x.u);
+    buf_store16(r, byte_off == OOB_OFF ? OOB_OFF : byte_off + 16, y.u);
   }
   DEV void get(float (&v)[8]) const {
     v[0] = a[0]; v[1] = a[1]; v[2] = a[2]; v[3] = a[3]; v[4] = b[0]; v[5] = b[1]; v[6] = b[2]; v[7] = b[3];

@@ -53,14 +53,21 @@ class _ViTFn(torch.autograd.Function):
 class ImageEncoder(nn.Module):
     r"""torchvision-topology ResNet with ``fc = Identity`` (reference encoder.py:28-65), or — a name starting with ``vit_`` — torchvision's
     ViT-B/32 / ViT-B/16 with ``heads = Identity`` (vit.py; built for ``image_size`` pixels, DATA.IMAGE_CROP_SIZE). ``pretrained`` weights cannot
-    be downloaded here (no network) and raise; ``frozen`` keeps all weights fixed and the encoder in eval mode."""
+    be downloaded here (no network) and raise; ``frozen`` keeps all weights fixed and the encoder in eval mode. ``patch_dropout`` (a ViT option,
+    MODEL.VISUAL.PATCH_DROPOUT) is the share of patches each image drops in training (FLIP); evaluation and a frozen encoder see every token."""
 
-    def __init__(self, img_enc_net: str = "resnet50", pretrained: bool = False, frozen: bool = False, image_size=224, **vit_kwargs):
+    def __init__(self, img_enc_net: str = "resnet50", pretrained: bool = False, frozen: bool = False, image_size=224, patch_dropout: float = 0.0,
+                 **vit_kwargs):
         """vit_kwargs: VisionTransformer's num_layers / hidden / heads / mlp_dim (small models for tests); a ResNet takes none."""
         super().__init__()
         if pretrained:
             raise RuntimeError("pretrained torchvision weights are not available offline; load a state_dict instead")
         self.is_vit = img_enc_net.startswith("vit_")
+        if patch_dropout != 0.0:
+            if not self.is_vit:
+                raise ValueError(f"clip_lite_amd: patch_dropout (MODEL.VISUAL.PATCH_DROPOUT) is a ViT option: {img_enc_net!r} has no patch tokens "
+                                 f"to drop; got {patch_dropout}")
+            vit_kwargs["patch_dropout"] = patch_dropout
         if vit_kwargs and not self.is_vit:
             raise TypeError(f"ImageEncoder({img_enc_net!r}): unexpected arguments {sorted(vit_kwargs)}")
         self.img_encoder = VisionTransformer(img_enc_net, image_size=image_size, **vit_kwargs) if self.is_vit else ResNet(img_enc_net)
@@ -75,7 +82,7 @@ class ImageEncoder(nn.Module):
         rt = _runtime_of(self)
         training = self.img_encoder.training and not self.frozen
         grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.img_encoder.parameters())
-        if self.is_vit:          # (no BatchNorm: training and eval compute the same thing, and there are no counters to bump)
+        if self.is_vit:          # (no BatchNorm, no counters to bump: training and eval differ by the patch dropout alone, where it is on)
             if grad:
                 x = _ViTFn.apply(image, rt.anchor, self, rt, training)
             else:

@@ -148,7 +148,8 @@ class VisualBackboneFactory(Factory):
     def from_config(cls, config: Config) -> ImageEncoder:
         # like the reference (factories.py:324-327) the network name is forwarded; a ViT is also built for one image size (its position embedding)
         _C = config
-        enc = cls.create(_C.MODEL.NAME, img_enc_net=_C.MODEL.VISUAL.NETWORK_NAME, image_size=_C.DATA.IMAGE_CROP_SIZE)
+        enc = cls.create(_C.MODEL.NAME, img_enc_net=_C.MODEL.VISUAL.NETWORK_NAME, image_size=_C.DATA.IMAGE_CROP_SIZE,
+                         patch_dropout=_C.MODEL.VISUAL.PATCH_DROPOUT)
         if enc.out_dim != _C.MODEL.VISUAL.FEATURE_SIZE:
             raise ValueError(f"MODEL.VISUAL.FEATURE_SIZE is {_C.MODEL.VISUAL.FEATURE_SIZE}, but {_C.MODEL.VISUAL.NETWORK_NAME} produces "
                              f"{enc.out_dim} features; set MODEL.VISUAL.FEATURE_SIZE to {enc.out_dim}")

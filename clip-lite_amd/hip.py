@@ -199,6 +199,10 @@ _SIGNATURES = {
     "clite_vit_tokens_bwd": [_I, _V, _V, _V, _V, _I, _I, _I, _V],
     "clite_vit_class_gather": [_I, _V, _V, _I, _I, _I, _V],
     "clite_vit_class_scatter": [_I, _V, _V, _I, _I, _I, _V],
+    "clite_vit_keep_indices": [_V, _V, _I, _I, _I, _U64, _U32, _V],
+    "clite_vit_patchify_keep": [_I, _V, _V, _V, _I, _I, _I, _I, _I, _V],
+    "clite_vit_tokens_keep_fwd": [_I, _V, _V, _V, _V, _V, _I, _I, _I, _I, _V],
+    "clite_vit_tokens_keep_bwd": [_I, _V, _V, _V, _V, _V, _I, _I, _I, _I, _V],
 }
 
 _lib = None
@@ -957,6 +961,45 @@ def vit_class_gather(dt, x, out, B, L, Cc):
 def vit_class_scatter(dt, d, dx, B, L, Cc):
     assert dx.numel() == B * L * Cc and d.numel() == B * Cc and d.dtype == dx.dtype == TORCH_DTYPE[dt] and d.is_contiguous() and dx.is_contiguous()
     check(lib().clite_vit_class_scatter(dt, p(d), p(dx), B, L, Cc, stream_ptr(d)), "vit_class_scatter")
+
+
+def _i32(t, n):
+    return t.dtype == torch.int32 and t.numel() == n and t.is_contiguous()
+
+
+def vit_keep_indices(idx, inv, B, P, Kk, seed, site):
+    """Patch dropout: idx int32 [B][Kk] = the kept patches of each sample in ascending order, inv int32 [B][P] = their positions or -1; the Kk
+    smallest keys of the (seed, site) stream, ties to the lower index (include/clite.h: clite_vit_keep_indices)."""
+    assert _i32(idx, B * Kk) and _i32(inv, B * P)
+    check(lib().clite_vit_keep_indices(p(idx), p(inv), B, P, Kk, seed, site, stream_ptr(idx)), "vit_keep_indices")
+
+
+def vit_patchify_keep(dt, img, idx, out, B, H, W, p_, Kk):
+    """vit_patchify on the kept patches: out [B * Kk][3 * p * p], row (b, k) = patch idx[b][k] (include/clite.h: clite_vit_patchify_keep)."""
+    if img.dtype != torch.float32 or tuple(img.shape) != (B, 3, H, W) or not img.is_contiguous():
+        raise ValueError(f"vit_patchify_keep: img must be a contiguous f32 tensor of shape {(B, 3, H, W)}")
+    if H % p_ or W % p_ or out.dtype != TORCH_DTYPE[dt] or out.numel() != B * Kk * 3 * p_ * p_ or not out.is_contiguous() or not _i32(idx, B * Kk):
+        raise ValueError(f"vit_patchify_keep: out must be a contiguous {TORCH_DTYPE[dt]} tensor of {B * Kk * 3 * p_ * p_} elements, idx int32 "
+                         f"[{B}][{Kk}] and p divide H and W")
+    check(lib().clite_vit_patchify_keep(dt, p(img), p(idx), p(out), B, H, W, p_, Kk, stream_ptr(img)), "vit_patchify_keep")
+
+
+def vit_tokens_keep_fwd(dt, e, cls, pos, idx, s0, B, P, Kk, Cc):
+    """s0 [B * (Kk + 1)][C] = class token / kept patch embeddings e [B * Kk][C] + their rows of pos [P + 1][C] (include/clite.h:
+    clite_vit_tokens_keep_fwd)."""
+    assert e.numel() == B * Kk * Cc and cls.numel() == Cc and pos.numel() == (P + 1) * Cc and s0.numel() == B * (Kk + 1) * Cc and _i32(idx, B * Kk)
+    assert all(t.dtype == TORCH_DTYPE[dt] and t.is_contiguous() for t in (e, cls, pos, s0))
+    check(lib().clite_vit_tokens_keep_fwd(dt, p(e), p(cls), p(pos), p(idx), p(s0), B, P, Kk, Cc, stream_ptr(e)), "vit_tokens_keep_fwd")
+
+
+def vit_tokens_keep_bwd(dt, ds0, inv, de, dpos, dcls, B, P, Kk, Cc):
+    """de [B * Kk][C] = the patch rows of ds0 [B * (Kk + 1)][C]; dpos f32 [P + 1][C] and dcls f32 [C] (either may be None) += the sums over the
+    samples that kept each position, in index order (include/clite.h: clite_vit_tokens_keep_bwd)."""
+    assert ds0.numel() == B * (Kk + 1) * Cc and de.numel() == B * Kk * Cc and ds0.dtype == de.dtype == TORCH_DTYPE[dt] and _i32(inv, B * P)
+    assert ds0.is_contiguous() and de.is_contiguous()
+    assert dpos is None or (dpos.dtype == torch.float32 and dpos.numel() == (P + 1) * Cc and dpos.is_contiguous())
+    assert dcls is None or (dcls.dtype == torch.float32 and dcls.numel() == Cc and dcls.is_contiguous())
+    check(lib().clite_vit_tokens_keep_bwd(dt, p(ds0), p(inv), p(de), p(dpos), p(dcls), B, P, Kk, Cc, stream_ptr(ds0)), "vit_tokens_keep_bwd")
 
 
 # ------------------------------------------------------------------------------------------------ loss / update

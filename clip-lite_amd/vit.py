@@ -12,6 +12,10 @@ Per layer (pre-LayerNorm order, torchvision EncoderBlock): y = LN1(x); qkv = y W
 (residual in the GEMM epilogue); z = LN2(x1); g = GELU(z W_0^T + b_0) with the pre-activation kept; x2 = x1 + g W_3^T + b_3. Backward is the
 mirror; the input gradient of a block half is LayerNorm_bwd(...) + the skip gradient, added by clite_add (clite_layernorm_bwd has no residual
 input). Dropout and attention dropout are 0, torchvision's default; another value raises.
+
+Patch dropout (FLIP, Li et al. 2023; `patch_dropout=r`): in training each image keeps kept_patches(P, r) of its P patches, chosen on the device
+from the pass's seed (clite_vit_keep_indices), plus the class token, and everything from the patch matrix on runs at that length through the
+same code (clite_vit_patchify_keep, clite_vit_tokens_keep_fwd / _bwd in place of the three full kernels). Evaluation sees every token.
 """
 import math
 
@@ -47,6 +51,15 @@ def token_count(name, H, W=None):
         raise ValueError(f"clip_lite_amd: {name} at {H} x {W} pixels has {L} tokens; the attention kernels support at most {MAX_TOKENS} "
                          f"(vit_b_32 up to 352 pixels, vit_b_16 up to 176)")
     return L
+
+
+def kept_patches(P, r):
+    """Patches each image keeps under patch dropout with ratio r (FLIP; open_clip's PatchDropout rule): max(1, int(P (1 - r))). Needs no device."""
+    r = float(r)
+    if not 0.0 <= r < 1.0:
+        raise ValueError(f"clip_lite_amd: patch_dropout (MODEL.VISUAL.PATCH_DROPOUT) is the share of patches dropped in training and must lie in "
+                         f"[0, 1); got {r}")
+    return max(1, int(P * (1.0 - r)))
 
 
 class _PatchProj(nn.Module):
@@ -126,14 +139,18 @@ class _Params:
 
 class VisionTransformer(nn.Module):
     """name: "vit_b_32" | "vit_b_16". image_size: the side of the square input, or (H, W). num_layers / hidden / heads / mlp_dim override the spec
-    (small test models); hidden == heads * 64 because the attention kernels are built for head size 64."""
+    (small test models); hidden == heads * 64 because the attention kernels are built for head size 64. patch_dropout: the share of patches each
+    image drops in training (FLIP): the tower then runs on kept_patches(P, r) patches + the class token; evaluation sees every token."""
 
     kind = "vit"
 
-    def __init__(self, name="vit_b_32", image_size=224, num_layers=None, hidden=None, heads=None, mlp_dim=None, dropout=0.0, attention_dropout=0.0):
+    def __init__(self, name="vit_b_32", image_size=224, num_layers=None, hidden=None, heads=None, mlp_dim=None, dropout=0.0, attention_dropout=0.0,
+                 patch_dropout=0.0):
         super().__init__()
         if name not in SPECS:
             raise ValueError(f"unsupported visual backbone {name!r}; supported ViTs: {sorted(SPECS)}")
+        kept_patches(1, patch_dropout)          # (raises for a ratio outside [0, 1))
+        self.patch_dropout = float(patch_dropout)
         if dropout != 0.0 or attention_dropout != 0.0:
             raise ValueError(f"clip_lite_amd: the ViT tower runs without dropout (torchvision's default); got dropout={dropout}, "
                              f"attention_dropout={attention_dropout}")
@@ -182,15 +199,34 @@ def vit_forward(rt, net, image, training=True):
     p, Cc, heads, inner = net.patch, net.hidden, net.heads, net.inner
     L = net.seq_length
     P, K = L - 1, 3 * p * p
-    M = B * L
-    patches = _alloc(rt, B * P, K)
-    hip.vit_patchify(dt, image, patches, B, H, W, p)
-    e = _alloc(rt, B * P, Cc)
-    hip.gemm_nt(dt, patches, A.w(net.conv_proj.weight).view(Cc, K), B * P, Cc, K, hip.epilogue(e, Cc, bias=net.conv_proj.bias))
-    x = _alloc(rt, M, Cc)
-    hip.vit_tokens_fwd(dt, e, A.w(net.class_token).view(Cc), A.w(net.encoder.pos_embedding).view(L, Cc), x, B, P, Cc)
+    cls, pos, wp = A.w(net.class_token).view(Cc), A.w(net.encoder.pos_embedding).view(L, Cc), A.w(net.conv_proj.weight).view(Cc, K)
+    keep = None
+    if training and net.patch_dropout > 0:
+        # patch dropout: the kept patches are chosen on the device from this pass's seed (inside a captured step from the indirect one, so every
+        # replay draws a fresh set), and everything from the patch matrix on runs on Kk patches per image: L is Kk + 1 from here
+        Kk = kept_patches(P, net.patch_dropout)
+        step = rt.next_step(True)
+        idx = torch.empty(B, Kk, device=rt.device, dtype=torch.int32)
+        inv = torch.empty(B, P, device=rt.device, dtype=torch.int32)
+        hip.vit_keep_indices(idx, inv, B, P, Kk, step.seed, step.site())
+        patches = _alloc(rt, B * Kk, K)
+        hip.vit_patchify_keep(dt, image, idx, patches, B, H, W, p, Kk)
+        e = _alloc(rt, B * Kk, Cc)
+        hip.gemm_nt(dt, patches, wp, B * Kk, Cc, K, hip.epilogue(e, Cc, bias=net.conv_proj.bias))
+        keep, L = (idx, inv, P, Kk), Kk + 1
+        M = B * L
+        x = _alloc(rt, M, Cc)
+        hip.vit_tokens_keep_fwd(dt, e, cls, pos, idx, x, B, P, Kk, Cc)
+    else:
+        M = B * L
+        patches = _alloc(rt, B * P, K)
+        hip.vit_patchify(dt, image, patches, B, H, W, p)
+        e = _alloc(rt, B * P, Cc)
+        hip.gemm_nt(dt, patches, wp, B * P, Cc, K, hip.epilogue(e, Cc, bias=net.conv_proj.bias))
+        x = _alloc(rt, M, Cc)
+        hip.vit_tokens_fwd(dt, e, cls, pos, x, B, P, Cc)
     mask = _ones_mask(rt, net, B, L)
-    ctx = {"B": B, "L": L, "patches": patches, "mask": mask, "layers": []}
+    ctx = {"B": B, "L": L, "patches": patches, "mask": mask, "layers": [], "keep": keep, "idx": keep and keep[0], "inv": keep and keep[1]}
     for layer in net.encoder.blocks():
         sa, (m0, m3) = layer.self_attention, layer.mlp.parts()
         y = _alloc(rt, M, Cc)
@@ -289,8 +325,15 @@ def vit_backward(rt, net, ctx, dfeat, defer=None):
             rt.grads_ready(layer)
             defer = own_group = hip.WgradGroup(rt.dt)
     # token assembly and the patch projection: conv_proj.weight's gradient is de^T patches, in the 4-D parameter's own [C][3][p][p] order
-    de = _alloc(rt, B * P, Cc)
-    hip.vit_tokens_bwd(dt, dh, de, A.g(net.encoder.pos_embedding).view(L, Cc), A.g(net.class_token).view(Cc), B, P, Cc)
+    # (under patch dropout over the kept patches only: B * Kk rows, the position embedding's gradient scattered through `inv`)
+    dpos, dcls = A.g(net.encoder.pos_embedding).view(net.seq_length, Cc), A.g(net.class_token).view(Cc)
+    if ctx["keep"] is not None:
+        _, inv, Pf, P = ctx["keep"]
+        de = _alloc(rt, B * P, Cc)
+        hip.vit_tokens_keep_bwd(dt, dh, inv, de, dpos, dcls, B, Pf, P, Cc)
+    else:
+        de = _alloc(rt, B * P, Cc)
+        hip.vit_tokens_bwd(dt, dh, de, dpos, dcls, B, P, Cc)
     _param_grads(rt, net.conv_proj.weight, net.conv_proj.bias, de, ctx["patches"], B * P, defer)
     if own_group is not None:
         own_group.launch()

@@ -865,6 +865,26 @@ int clite_vit_tokens_bwd(int dtype, const void* ds0, void* de, float* dpos, floa
 int clite_vit_class_gather(int dtype, const void* x, void* out, int B, int L, int C, void* stream);
 int clite_vit_class_scatter(int dtype, const void* d, void* dx, int B, int L, int C, void* stream);
 
+/* ---- Patch dropout (FLIP, Li et al. 2023; open_clip's PatchDropout): in training each image keeps Kk of its P patches plus the class token, and
+ * the tower runs at L' = Kk + 1 tokens. Additive to ABI v12. No float atomics; the same bits in both settings of clite_set_deterministic.
+ * The kept set of sample b: key[t] = the 24-bit uniform of element b * Ppad + t of the (seed, site) stream of rng_uniform4 (csrc/rng.h),
+ * Ppad = P rounded up to a multiple of 4; rank[t] = the number of u with key[u] < key[t], or key[u] == key[t] and u < t; patch t is kept iff
+ * rank[t] < Kk. idx int32 [B][Kk] lists the kept patches in ascending order, inv int32 [B][P] holds the position of t in idx[b] or -1.
+ * (seed, site) as for every dropout site (CLITE_SEED_INDIRECT). Returns -1 for B < 1, P outside 1 .. 128, Kk outside 1 .. P or a null pointer. */
+int clite_vit_keep_indices(int32_t* idx, int32_t* inv, int B, int P, int Kk, uint64_t seed, uint32_t site, void* stream);
+/* clite_vit_patchify on the kept patches only: out [B * Kk][3 * p * p], row (b, k) = the patch idx[b][k] of image b; the rest of the image is
+ * not read. -1 also for Kk outside 1 .. (H/p)(W/p). An idx entry outside 0 .. P - 1 leaves its row unwritten. */
+int clite_vit_patchify_keep(int dtype, const float* img, const int32_t* idx, void* out, int B, int H, int W, int p, int Kk, void* stream);
+/* Token assembly at L' = Kk + 1: s0[b][0] = cls + pos[0], s0[b][1 + k] = e[b][k] + pos[1 + idx[b][k]]; e [B * Kk][C], pos [P + 1][C],
+ * s0 [B * L'][C]; f32 sum, one rounding. Equal to clite_vit_tokens_fwd followed by a gather of the rows 0 and 1 + idx[b]. */
+int clite_vit_tokens_keep_fwd(int dtype, const void* e, const void* cls, const void* pos, const int32_t* idx, void* s0, int B, int P, int Kk, int C,
+                              void* stream);
+/* Its backward, through inv: de[b][k] = ds0[b][1 + k]; dpos[1 + t] += the sum over the samples that kept t of their row, in ascending b;
+ * dpos[0] and dcls += the sum over b of row 0 (f32 [P + 1][C] and [C], either may be NULL). One thread owns a (position, 8 columns) slot. The
+ * dpos row of a position no sample kept is not touched. -1 also for a ds0 of 0xF0000000 bytes or more in f32 (ds0 and de are addressed through one buffer resource each). */
+int clite_vit_tokens_keep_bwd(int dtype, const void* ds0, const int32_t* inv, void* de, float* dpos, float* dcls, int B, int P, int Kk, int C,
+                              void* stream);
+
 #ifdef __cplusplus
 }
 #endif
