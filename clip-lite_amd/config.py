@@ -147,6 +147,8 @@ class Config(object):
         _C.MODEL.TEXTUAL.FEATURE_SIZE = 768
         _C.MODEL.TEXTUAL.SELF_SUPERVISED = False
         _C.MODEL.TEXTUAL.NUM_HIDDEN_LAYERS = 12
+        # (not a reference key) CLIP text tower only (NETWORK_NAME clip_text_b): rows of its positional embedding = the longest caption it takes; at most 128
+        _C.MODEL.TEXTUAL.CONTEXT_LENGTH = 77
         _C.MODEL.LOSS = Node()
         _C.MODEL.LOSS.NAME = "jsd"
         _C.MODEL.LOSS.TYPE = "dot"
@@ -195,6 +197,8 @@ class Config(object):
     def add_derived_params(self):
         """RUN_ID doubles as the checkpoint sub-directory name (reference config.py:223-250); field order kept."""
         c = self._C
+        if not 1 <= int(c.MODEL.TEXTUAL.CONTEXT_LENGTH) <= 128:
+            raise ValueError(f"MODEL.TEXTUAL.CONTEXT_LENGTH is {c.MODEL.TEXTUAL.CONTEXT_LENGTH}; the attention kernels support 1 to 128 tokens")
         fields = [("V", c.MODEL.VISUAL.NETWORK_NAME), ("T", c.MODEL.TEXTUAL.NAME), ("Ty", c.MODEL.LOSS.TYPE),
                   ("Vs", c.MODEL.VISUAL.SELF_SUPERVISED), ("Ts", c.MODEL.TEXTUAL.SELF_SUPERVISED), ("N", c.DATA.NEGATIVE_SAMPLING),
                   ("B", c.OPTIM.BATCH_SIZE), ("O", c.OPTIM.OPTIMIZER_NAME), ("B", c.OPTIM.BATCH_SIZE), ("D", c.OPTIM.LR_DECAY_NAME),

@@ -1164,6 +1164,653 @@ __global__ __launch_bounds__(64 * NT) void attention_long_mfma_bwd_kernel(const 
   }
 }
 
+// ------------------------------------------------------------------------------------------------ causal attention (CLIP text tower), L <= 128
+// The four kernel families above with one more condition on a score: query i sees key j iff j <= i (and the key mask allows it). A key behind the
+// diagonal is treated as a key beyond L is: its score is -inf, so it takes no part in the softmax and its probability is an exact zero. Key 0 is
+// visible to every query (mask[b][0] == 1 is the entry points' precondition), so no row is empty. There is no dropout and no bias. The kernels
+// are separate ones: the text of the non-causal kernels, and so their code, is what it was.
+struct AttnCausalSmem { float q[AT_L * AT_PQ], k[AT_L * AT_PQ], v[AT_L * AT_PQ], p[AT_L * AT_PP]; };
+struct AttnCausalBwdSmem { AttnCausalSmem f; float dO[AT_L * AT_PQ], dS[AT_L * AT_PP]; };
+
+// attn_probs with the causal test: p[i][j] = 0 for j > i
+DEV void attn_probs_causal(AttnCausalSmem& sm, const int64_t* mask_row, int L, int lane) {
+  const int j = lane & 31, half = lane >> 5;
+  const bool jvalid = j < L;
+  float madd = 0.f;
+  if (jvalid && mask_row) madd = mask_row[j] != 0 ? 0.f : AT_NEG;
+  for (int i0 = 0; i0 < AT_L; i0 += 2) {
+    int i = i0 + half;
+    const bool seen = jvalid && j <= i;
+    float s = 0.f;
+#pragma unroll 16
+    for (int d = 0; d < AT_D; ++d) s += sm.q[i * AT_PQ + d] * sm.k[j * AT_PQ + d];
+    s = s * 0.125f + madd;
+    if (!seen) s = -INFINITY;
+    float mx = s;
+#pragma unroll
+    for (int m = 16; m >= 1; m >>= 1) mx = fmaxf(mx, wave_shfl_xor(mx, m));
+    float e = seen ? __expf(s - mx) : 0.f;
+    float den = e;
+#pragma unroll
+    for (int m = 16; m >= 1; m >>= 1) den += wave_shfl_xor(den, m);
+    sm.p[i * AT_PP + j] = (i < L) ? e / den : 0.f;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(64) void attention_causal_fwd_kernel(const T* qkv, const int64_t* mask, T* ctx, int B, int L, int H) {
+  __shared__ AttnCausalSmem sm;
+  const int lane = threadIdx.x;
+  const int b = blockIdx.x / H, h = blockIdx.x % H;
+  const size_t ld = (size_t)3 * H * AT_D;
+  const T* base = qkv + (size_t)b * L * ld + h * AT_D;
+  attn_load_rows(base, ld, L, sm.q, lane);
+  attn_load_rows(base + H * AT_D, ld, L, sm.k, lane);
+  attn_load_rows(base + 2 * H * AT_D, ld, L, sm.v, lane);
+  __syncthreads();
+  attn_probs_causal(sm, mask ? mask + (size_t)b * L : nullptr, L, lane);
+  __syncthreads();
+  for (int i = 0; i < L; ++i) {
+    float o = 0.f;
+    for (int j = 0; j <= i; ++j) o += sm.p[i * AT_PP + j] * sm.v[j * AT_PQ + lane];
+    al_store(ctx + ((size_t)b * L + i) * ((size_t)H * AT_D) + h * AT_D + lane, o);
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(64) void attention_causal_bwd_kernel(const T* qkv, const int64_t* mask, const T* dctx, T* dqkv, int B, int L, int H) {
+  __shared__ AttnCausalBwdSmem sm;
+  const int lane = threadIdx.x;
+  const int b = blockIdx.x / H, h = blockIdx.x % H;
+  const size_t ld = (size_t)3 * H * AT_D;
+  const T* base = qkv + (size_t)b * L * ld + h * AT_D;
+  attn_load_rows(base, ld, L, sm.f.q, lane);
+  attn_load_rows(base + H * AT_D, ld, L, sm.f.k, lane);
+  attn_load_rows(base + 2 * H * AT_D, ld, L, sm.f.v, lane);
+  attn_load_rows(dctx + (size_t)b * L * ((size_t)H * AT_D) + h * AT_D, (size_t)H * AT_D, L, sm.dO, lane);
+  __syncthreads();
+  attn_probs_causal(sm.f, mask ? mask + (size_t)b * L : nullptr, L, lane);
+  __syncthreads();
+  const int j = lane & 31, half = lane >> 5;
+  // dP[i][j] = sum_d dO[i][d] V[j][d];  dS = P * (dP - sum_j dP*P): zero behind the diagonal, where P is
+  for (int i0 = 0; i0 < AT_L; i0 += 2) {
+    int i = i0 + half;
+    float dp = 0.f;
+#pragma unroll 16
+    for (int d = 0; d < AT_D; ++d) dp += sm.dO[i * AT_PQ + d] * sm.f.v[j * AT_PQ + d];
+    float pij = sm.f.p[i * AT_PP + j];
+    float t = dp * pij;
+#pragma unroll
+    for (int m = 16; m >= 1; m >>= 1) t += wave_shfl_xor(t, m);
+    sm.dS[i * AT_PP + j] = pij * (dp - t);
+  }
+  __syncthreads();
+  // lane = d.  dQ[r] sums the keys t <= r, dK[r] and dV[r] the queries t >= r, in ascending order
+  T* obase = dqkv + (size_t)b * L * ld + h * AT_D;
+  for (int r = 0; r < L; ++r) {
+    float dq = 0.f, dk = 0.f, dv = 0.f;
+    for (int t = 0; t <= r; ++t) dq += sm.dS[r * AT_PP + t] * sm.f.k[t * AT_PQ + lane];
+    for (int t = r; t < L; ++t) {
+      dk += sm.dS[t * AT_PP + r] * sm.f.q[t * AT_PQ + lane];
+      dv += sm.f.p[t * AT_PP + r] * sm.dO[t * AT_PQ + lane];
+    }
+    T* o = obase + (size_t)r * ld + lane;
+    al_store(o, dq * 0.125f);
+    al_store(o + H * AT_D, dk * 0.125f);
+    al_store(o + 2 * H * AT_D, dv);
+  }
+}
+
+// ---- bf16 MFMA, L <= 32: attention_mfma_{fwd,bwd}_kernel with the element-wise test on the one tile
+struct AmCausalBwdSmem { char q[32 * AM_PI], k[32 * AM_PI], d[32 * AM_PI], t[32 * AM_PT]; float madd[32]; };
+
+__global__ __launch_bounds__(256) void attention_causal_mfma_fwd_kernel(const bf16* qkv, const int64_t* mask, bf16* ctx, int B, int L, int H) {
+  __shared__ __attribute__((aligned(16))) AmFwdSmem sm[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int bh = blockIdx.x * 4 + wave;
+  const bool live = bh < B * H;
+  if (!live) bh = B * H - 1;
+  const int b = bh / H, h = bh % H;
+  const size_t ld = (size_t)3 * H * 64;
+  const bf16* qb = qkv + (size_t)b * L * ld + h * 64;
+  AmFwdSmem& S = sm[wave];
+  am_load_image(qb + 2 * H * 64, ld, L, S.v, lane);
+  if (lane < 32) S.madd[lane] = al_madd(mask, b, L, lane);
+  f32x16 acc;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks)      // S^T[j][i] = sum_d K[j][d] Q[i][d]
+    acc = mfma32_bf16(am_frag_rows(qb + H * 64, ld, L, ks, lane), am_frag_rows(qb, ld, L, ks, lane), acc);
+  __syncthreads();
+  // softmax over the keys j = am_row(r, lane) <= i for the query i = lane&31
+  const int i = lane & 31;
+  float mx = -INFINITY;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {
+    acc[r] = am_row(r, lane) > i ? -INFINITY : acc[r] * 0.125f + S.madd[am_row(r, lane)];
+    mx = fmaxf(mx, acc[r]);
+  }
+  mx = fmaxf(mx, wave_shfl_xor(mx, 32));
+  float den = 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { acc[r] = __expf(acc[r] - mx); den += acc[r]; }
+  den += wave_shfl_xor(den, 32);
+  const float inv = 1.0f / den;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) acc[r] *= inv;
+  // O^T[d][i] = sum_j V^T[d][j] P^T[j][i]
+#pragma unroll
+  for (int db = 0; db < 2; ++db) {
+    f32x16 o;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[r] = 0.f;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) o = mfma32_bf16(am_frag_tr_acc<AM_PI>(S.v, db * 32, s, lane), am_acc_frag(acc, s), o);
+    if (live) am_store_T(ctx + (size_t)b * L * ((size_t)H * 64) + h * 64, (size_t)H * 64, L, db * 32, o, 1.f, lane);
+  }
+}
+
+__global__ __launch_bounds__(128) void attention_causal_mfma_bwd_kernel(const bf16* qkv, const int64_t* mask, const bf16* dctx, bf16* dqkv, int B, int L, int H) {
+  __shared__ __attribute__((aligned(16))) AmCausalBwdSmem sm[2];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int bh = blockIdx.x * 2 + wave;
+  const bool live = bh < B * H;
+  if (!live) bh = B * H - 1;
+  const int b = bh / H, h = bh % H;
+  const size_t ld = (size_t)3 * H * 64, ldc = (size_t)H * 64;
+  const bf16* qb = qkv + (size_t)b * L * ld + h * 64;
+  const bf16* dob = dctx + (size_t)b * L * ldc + h * 64;
+  AmCausalBwdSmem& S = sm[wave];
+  am_load_image(qb, ld, L, S.q, lane);
+  am_load_image(qb + H * 64, ld, L, S.k, lane);
+  am_load_image(dob, ldc, L, S.d, lane);
+  if (lane < 32) S.madd[lane] = al_madd(mask, b, L, lane);
+  f32x16 p, dp;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { p[r] = 0.f; dp[r] = 0.f; }
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    p = mfma32_bf16(am_frag_rows(qb, ld, L, ks, lane), am_frag_rows(qb + H * 64, ld, L, ks, lane), p);            // S[i][j]
+    dp = mfma32_bf16(am_frag_rows(dob, ldc, L, ks, lane), am_frag_rows(qb + 2 * H * 64, ld, L, ks, lane), dp);    // dP[i][j] = dO V^T
+  }
+  __syncthreads();
+  const int j = lane & 31;
+  const float madd = S.madd[j];
+  f32x16 ds;
+#pragma unroll
+  for (int r = 0; r < 16; ++r) {      // softmax over j <= i = across the 32 lanes of a half, per register row i
+    const int i = am_row(r, lane);
+    const float s = j > i ? -INFINITY : p[r] * 0.125f + madd;
+    float mx = s;
+#pragma unroll
+    for (int m = 16; m >= 1; m >>= 1) mx = fmaxf(mx, wave_shfl_xor(mx, m));
+    float e = __expf(s - mx);
+    float den = e;
+#pragma unroll
+    for (int m = 16; m >= 1; m >>= 1) den += wave_shfl_xor(den, m);
+    float pr = (i < L) ? e / den : 0.f;
+    float t = dp[r] * pr;
+#pragma unroll
+    for (int m = 16; m >= 1; m >>= 1) t += wave_shfl_xor(t, m);
+    p[r] = pr;
+    ds[r] = pr * (dp[r] - t);
+  }
+  // dS^T image for dQ: T[j][i] = dS[i][j]
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    union { bf16 e[4]; u32x2 u; } pk;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) pk.e[e] = f2bf(ds[4 * g + e]);
+    *(u32x2*)(S.t + j * AM_PT + (8 * g + 4 * (lane >> 5)) * 2) = pk.u;
+  }
+  __syncthreads();
+  bf16* ob = dqkv + (size_t)b * L * ld + h * 64;
+#pragma unroll
+  for (int db = 0; db < 2; ++db) {
+    f32x16 dv, dk, dq;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { dv[r] = 0.f; dk[r] = 0.f; dq[r] = 0.f; }
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      dv = mfma32_bf16(am_frag_tr_acc<AM_PI>(S.d, db * 32, s, lane), am_acc_frag(p, s), dv);       // dV^T[d][j] = sum_i dO^T[d][i] P[i][j]
+      dk = mfma32_bf16(am_frag_tr_acc<AM_PI>(S.q, db * 32, s, lane), am_acc_frag(ds, s), dk);      // dK^T[d][j] = sum_i Q^T[d][i] dS[i][j]
+      dq = mfma32_bf16(am_frag_tr<AM_PI>(S.k, db * 32, s, lane), am_frag_tr<AM_PT>(S.t, 0, s, lane), dq);   // dQ^T[d][i] = sum_j K^T[d][j] dS^T[j][i]
+    }
+    if (live) {
+      am_store_T(ob + 2 * H * 64, ld, L, db * 32, dv, 1.f, lane);
+      am_store_T(ob + H * 64, ld, L, db * 32, dk, 0.125f, lane);
+      am_store_T(ob, ld, L, db * 32, dq, 0.125f, lane);
+    }
+  }
+}
+
+// ---- exact f32 on the VALU, 33..128: attention_long_{fwd,bwd}_kernel; a score row ends at its diagonal, a score column begins there. The upper
+// half of the lanes' keys (j = lane + 64) is not formed for a query below 64, nor the lower half of the queries for a key from 64 on.
+struct AlCausalBwdSmem {
+  float q[AL_L * AT_PQ], k[AL_L * AT_PQ], v[AL_L * AT_PQ], dO[AL_L * AT_PQ];
+  float madd[AL_L], mx[AL_L], den[AL_L], t[AL_L];
+  float vec[4][2][2][AL_L];                            // [wave][iteration parity][dS | P]
+};
+
+template <typename T>
+__global__ __launch_bounds__(256) void attention_causal_long_fwd_kernel(const T* qkv, const int64_t* mask, T* ctx, int B, int L, int H) {
+  __shared__ AlSmem sm;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int bh = blockIdx.x, b = bh / H, h = bh % H;
+  const size_t ld = (size_t)3 * H * AT_D;
+  const T* base = qkv + (size_t)b * L * ld + h * AT_D;
+  al_load_rows(base, ld, L, sm.q, tid);
+  al_load_rows(base + H * AT_D, ld, L, sm.k, tid);
+  al_load_rows(base + 2 * H * AT_D, ld, L, sm.v, tid);
+  if (tid < AL_L) sm.madd[tid] = al_madd(mask, b, L, tid);
+  __syncthreads();
+  for (int it = 0; it < (L + 3) / 4; ++it) {
+    const int i = it * 4 + wave;
+    float* row = sm.row[wave][it & 1];
+    if (i < L) {
+      float s0 = -INFINITY, s1 = -INFINITY;
+      if (lane <= i) s0 = al_dot(sm.q + i * AT_PQ, sm.k + lane * AT_PQ) * 0.125f + sm.madd[lane];
+      if (i >= 64 && lane + 64 <= i) s1 = al_dot(sm.q + i * AT_PQ, sm.k + (lane + 64) * AT_PQ) * 0.125f + sm.madd[lane + 64];
+      const float mx = wave_max(fmaxf(s0, s1));
+      const float e0 = __expf(s0 - mx), e1 = __expf(s1 - mx);      // keys > i and keys >= L: exp(-inf) = 0
+      const float den = wave_sum(e0 + e1);
+      row[lane] = e0 / den;
+      row[lane + 64] = e1 / den;
+    }
+    __syncthreads();
+    if (i < L) {
+      float o = 0.f;
+      for (int j = 0; j <= i; ++j) o += row[j] * sm.v[j * AT_PQ + lane];
+      al_store(ctx + ((size_t)b * L + i) * ((size_t)H * AT_D) + h * AT_D + lane, o);
+    }
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void attention_causal_long_bwd_kernel(const T* qkv, const int64_t* mask, const T* dctx, T* dqkv, int B, int L, int H) {
+  __shared__ AlCausalBwdSmem sm;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int bh = blockIdx.x, b = bh / H, h = bh % H;
+  const size_t ld = (size_t)3 * H * AT_D;
+  const T* base = qkv + (size_t)b * L * ld + h * AT_D;
+  al_load_rows(base, ld, L, sm.q, tid);
+  al_load_rows(base + H * AT_D, ld, L, sm.k, tid);
+  al_load_rows(base + 2 * H * AT_D, ld, L, sm.v, tid);
+  al_load_rows(dctx + (size_t)b * L * ((size_t)H * AT_D) + h * AT_D, (size_t)H * AT_D, L, sm.dO, tid);
+  if (tid < AL_L) sm.madd[tid] = al_madd(mask, b, L, tid);
+  __syncthreads();
+  T* obase = dqkv + (size_t)b * L * ld + h * AT_D;
+  const int iters = (L + 3) / 4;
+  // query rows: P, dP = dO V^T, dS = P * (dP - sum_j dP*P) over the keys j <= i; dQ[i] = dS[i] K / 8. The row's softmax statistics stay in LDS.
+  for (int it = 0; it < iters; ++it) {
+    const int i = it * 4 + wave;
+    float* ds = sm.vec[wave][it & 1][0];
+    if (i < L) {
+      float s0 = -INFINITY, s1 = -INFINITY, dp0 = 0.f, dp1 = 0.f;
+      if (lane <= i) {
+        s0 = al_dot(sm.q + i * AT_PQ, sm.k + lane * AT_PQ) * 0.125f + sm.madd[lane];
+        dp0 = al_dot(sm.dO + i * AT_PQ, sm.v + lane * AT_PQ);
+      }
+      if (i >= 64 && lane + 64 <= i) {
+        s1 = al_dot(sm.q + i * AT_PQ, sm.k + (lane + 64) * AT_PQ) * 0.125f + sm.madd[lane + 64];
+        dp1 = al_dot(sm.dO + i * AT_PQ, sm.v + (lane + 64) * AT_PQ);
+      }
+      const float mx = wave_max(fmaxf(s0, s1));
+      const float e0 = __expf(s0 - mx), e1 = __expf(s1 - mx);
+      const float den = wave_sum(e0 + e1);
+      const float p0 = e0 / den, p1 = e1 / den;
+      const float t = wave_sum(dp0 * p0 + dp1 * p1);
+      ds[lane] = p0 * (dp0 - t);
+      ds[lane + 64] = p1 * (dp1 - t);
+      if (lane == 0) { sm.mx[i] = mx; sm.den[i] = den; sm.t[i] = t; }
+    }
+    __syncthreads();
+    if (i < L) {
+      float dq = 0.f;
+      for (int j = 0; j <= i; ++j) dq += ds[j] * sm.k[j * AT_PQ + lane];
+      al_store(obase + (size_t)i * ld + lane, dq * 0.125f);
+    }
+  }
+  __syncthreads();
+  // key rows: column j of dS and of P from the saved statistics for the queries i >= j (lane = query i, i + 64); dK[j] = dS[:, j]^T Q / 8,
+  // dV[j] = P[:, j]^T dO, summed over those queries in ascending order
+  for (int it = 0; it < iters; ++it) {
+    const int j = it * 4 + wave;
+    float* ds = sm.vec[wave][it & 1][0];
+    float* pd = sm.vec[wave][it & 1][1];
+    if (j < L) {
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        if (half == 0 && j >= 64) continue;      // (queries below 64 do not see this key, and the sums below start at j)
+        const int i = lane + 64 * half;
+        float dsv = 0.f, pv = 0.f;
+        if (i < L && i >= j) {
+          const float s = al_dot(sm.q + i * AT_PQ, sm.k + j * AT_PQ) * 0.125f + sm.madd[j];
+          pv = __expf(s - sm.mx[i]) / sm.den[i];
+          dsv = pv * (al_dot(sm.dO + i * AT_PQ, sm.v + j * AT_PQ) - sm.t[i]);
+        }
+        ds[i] = dsv;
+        pd[i] = pv;
+      }
+    }
+    __syncthreads();
+    if (j < L) {
+      float dk = 0.f, dv = 0.f;
+      for (int i = j; i < L; ++i) {
+        dk += ds[i] * sm.q[i * AT_PQ + lane];
+        dv += pd[i] * sm.dO[i * AT_PQ + lane];
+      }
+      al_store(obase + (size_t)j * ld + H * AT_D + lane, dk * 0.125f);
+      al_store(obase + (size_t)j * ld + 2 * H * AT_D + lane, dv);
+    }
+  }
+}
+
+// ---- bf16 MFMA, 33..128: attention_long_mfma_{fwd,bwd}_kernel on the lower triangle of the NT x NT tile products. Wave w (query tile w) forms the
+// scores against the key tiles 0..w only — 3 of 4 products at NT = 2, 6 of 9 at NT = 3, 10 of 16 at NT = 4 — and only the diagonal tile t = w
+// applies the element-wise test. Backward: dQ of query tile w sums the key tiles 0..w, dK / dV of key tile w the query tiles w..NT-1 in ascending
+// order; the [key][query] images are written and read on that triangle only.
+// Every wave runs the matrix products in a body compiled for ITS tile index W (a switch on the wave index around straight-line code): with the tile loops bounded by a
+// run-time wave index instead, each product sat in a basic block of its own behind its own loads, and the one wave a SIMD holds here waited out
+// every LDS and global latency in turn — that form ran the backward 1.3 - 1.5 x SLOWER than the non-causal kernel. The
+// workgroup barriers stay outside the switches, and the first one behind the score products, which read global memory only: the fill of the
+// LDS images overlaps them, as in the non-causal kernels.
+template <int NT> struct AlmCausalBwdSmem {
+  static constexpr int PT = 64 * NT + 16;      // [32 NT][32 NT] bf16 image pitch
+  char q[32 * NT * AM_PI], k[32 * NT * AM_PI], d[32 * NT * AM_PI], ts[32 * NT * PT], tp[32 * NT * PT];
+  float madd[32 * NT];
+};
+
+// forward of query tile W, from global memory alone (it runs while the V image is still on its way into LDS): S^T = K Q^T over the key tiles 0..W
+template <int NT, int W>
+DEV void almc_fwd_scores(const bf16* qb, f32x16 (&acc)[NT], int L, int H, int lane) {
+  const size_t ld = (size_t)3 * H * 64;
+  const int Lq = L - 32 * W;      // rows of this query tile inside the sample (> 0: L > 32 (NT - 1))
+  bf16x8 qf[4];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) qf[ks] = am_frag_rows(qb + (size_t)32 * W * ld, ld, Lq, ks, lane);
+#pragma unroll
+  for (int t = 0; t <= W; ++t) {      // S^T[j][i] = sum_d K[j][d] Q[i][d], key tile t
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) acc[t] = mfma32_bf16(am_frag_rows(qb + H * 64 + (size_t)32 * t * ld, ld, L - 32 * t, ks, lane), qf[ks], acc[t]);
+  }
+}
+// ... then the softmax over the keys j <= i (W + 1 accumulators x the two lane halves) for the query i = 32 W + (lane & 31), and O^T = V^T P^T
+template <int NT, int W>
+DEV void almc_fwd_out(f32x16 (&acc)[NT], bf16* ctx_tile, const AlmFwdSmem<NT>& S, int L, int H, int lane) {
+  const size_t ldc = (size_t)H * 64;
+  const int Lq = L - 32 * W;
+  const int il = lane & 31;
+  float mx = -INFINITY;
+#pragma unroll
+  for (int t = 0; t <= W; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      const float s = acc[t][r] * 0.125f + S.madd[32 * t + am_row(r, lane)];
+      acc[t][r] = (t == W && am_row(r, lane) > il) ? -INFINITY : s;
+      mx = fmaxf(mx, acc[t][r]);
+    }
+  mx = fmaxf(mx, wave_shfl_xor(mx, 32));
+  float den = 0.f;
+#pragma unroll
+  for (int t = 0; t <= W; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { acc[t][r] = __expf(acc[t][r] - mx); den += acc[t][r]; }
+  den += wave_shfl_xor(den, 32);
+  const float inv = 1.0f / den;
+#pragma unroll
+  for (int t = 0; t <= W; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] *= inv;
+  // O^T[d][i] = sum_j V^T[d][j] P^T[j][i], key tiles in ascending order
+#pragma unroll
+  for (int db = 0; db < 2; ++db) {
+    f32x16 o;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) o[r] = 0.f;
+#pragma unroll
+    for (int t = 0; t <= W; ++t)
+#pragma unroll
+      for (int s = 0; s < 2; ++s) o = mfma32_bf16(am_frag_tr_acc<AM_PI>(S.v + 32 * t * AM_PI, db * 32, s, lane), am_acc_frag(acc[t], s), o);
+    am_store_T(ctx_tile, ldc, Lq, db * 32, o, 1.f, lane);
+  }
+}
+
+template <int NT>
+__global__ __launch_bounds__(64 * NT) void attention_causal_long_mfma_fwd_kernel(const bf16* qkv, const int64_t* mask, bf16* ctx, int B, int L, int H) {
+  __shared__ __attribute__((aligned(16))) AlmFwdSmem<NT> S;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int bh = blockIdx.x, b = bh / H, h = bh % H;
+  const size_t ld = (size_t)3 * H * 64, ldc = (size_t)H * 64;
+  const bf16* qb = qkv + (size_t)b * L * ld + h * 64;
+  alm_load_image<NT>(qb + 2 * H * 64, ld, L, S.v, tid);
+  if (tid < 32 * NT) S.madd[tid] = al_madd(mask, b, L, tid);
+  f32x16 acc[NT];
+  switch (wave) {
+    case 0: almc_fwd_scores<NT, 0>(qb, acc, L, H, lane); break;
+    case 1: almc_fwd_scores<NT, 1>(qb, acc, L, H, lane); break;
+    case 2: if constexpr (NT > 2) almc_fwd_scores<NT, 2>(qb, acc, L, H, lane); break;
+    default: if constexpr (NT > 3) almc_fwd_scores<NT, 3>(qb, acc, L, H, lane); break;
+  }
+  __syncthreads();
+  bf16* ct = ctx + ((size_t)b * L + 32 * wave) * ldc + h * 64;
+  switch (wave) {
+    case 0: almc_fwd_out<NT, 0>(acc, ct, S, L, H, lane); break;
+    case 1: almc_fwd_out<NT, 1>(acc, ct, S, L, H, lane); break;
+    case 2: if constexpr (NT > 2) almc_fwd_out<NT, 2>(acc, ct, S, L, H, lane); break;
+    default: if constexpr (NT > 3) almc_fwd_out<NT, 3>(acc, ct, S, L, H, lane); break;
+  }
+}
+
+// backward, first part, of query tile W, from global memory alone (the images are still on their way into LDS): S = Q K^T and dP = dO V^T
+// against the key tiles 0..W
+template <int NT, int W>
+DEV void almc_bwd_scores(const bf16* qb, const bf16* dob, f32x16 (&p)[NT], f32x16 (&dp)[NT], int L, int H, int lane) {
+  const size_t ld = (size_t)3 * H * 64, ldc = (size_t)H * 64;
+  const int Lq = L - 32 * W;
+  bf16x8 qf[4], dof[4];
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) {
+    qf[ks] = am_frag_rows(qb + (size_t)32 * W * ld, ld, Lq, ks, lane);
+    dof[ks] = am_frag_rows(dob + (size_t)32 * W * ldc, ldc, Lq, ks, lane);
+  }
+#pragma unroll
+  for (int t = 0; t <= W; ++t) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { p[t][r] = 0.f; dp[t][r] = 0.f; }
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      p[t] = mfma32_bf16(qf[ks], am_frag_rows(qb + H * 64 + (size_t)32 * t * ld, ld, L - 32 * t, ks, lane), p[t]);            // S[i][j]
+      dp[t] = mfma32_bf16(dof[ks], am_frag_rows(qb + 2 * H * 64 + (size_t)32 * t * ld, ld, L - 32 * t, ks, lane), dp[t]);     // dP[i][j] = dO V^T
+    }
+  }
+}
+// ... then the softmax and dS; leaves dS^T and P^T of the tile's 32 queries in the images. ONE body for all waves (four specialised copies of this
+// VALU-heavy part made the NT = 4 kernel 63 KB of code, which does not stay in the instruction cache with four waves in four places of it): the
+// key tiles are the outer loop of every stage, so a wave-uniform `t <= wave` guards 16 register rows of straight-line code at a time.
+template <int NT>
+DEV void almc_bwd_softmax(f32x16 (&p)[NT], f32x16 (&dp)[NT], AlmCausalBwdSmem<NT>& S, int L, int wave, int lane) {
+  constexpr int PT = AlmCausalBwdSmem<NT>::PT;
+  const int Lq = L - 32 * wave;
+  const int jl = lane & 31;
+  float mx[16], den[16], tt[16];      // per register row i = am_row(r, lane), over j <= i = across the 32 lanes of a half and the tiles t <= wave
+#pragma unroll
+  for (int r = 0; r < 16; ++r) { mx[r] = -INFINITY; den[r] = 0.f; tt[r] = 0.f; }
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+    if (t <= wave) {
+      const float madd = S.madd[32 * t + jl];
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        p[t][r] = (t == wave && jl > am_row(r, lane)) ? -INFINITY : p[t][r] * 0.125f + madd;
+        mx[r] = fmaxf(mx[r], p[t][r]);
+      }
+    }
+#pragma unroll
+  for (int r = 0; r < 16; ++r)
+#pragma unroll
+    for (int m = 16; m >= 1; m >>= 1) mx[r] = fmaxf(mx[r], wave_shfl_xor(mx[r], m));
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+    if (t <= wave) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) { p[t][r] = __expf(p[t][r] - mx[r]); den[r] += p[t][r]; }
+    }
+#pragma unroll
+  for (int r = 0; r < 16; ++r)
+#pragma unroll
+    for (int m = 16; m >= 1; m >>= 1) den[r] += wave_shfl_xor(den[r], m);
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+    if (t <= wave) {
+#pragma unroll
+      for (int r = 0; r < 16; ++r) {
+        p[t][r] = (am_row(r, lane) < Lq) ? p[t][r] / den[r] : 0.f;      // P
+        tt[r] += dp[t][r] * p[t][r];
+      }
+    }
+#pragma unroll
+  for (int r = 0; r < 16; ++r)
+#pragma unroll
+    for (int m = 16; m >= 1; m >>= 1) tt[r] += wave_shfl_xor(tt[r], m);
+  // dS, and the images on the triangle: ts[j][i] = dS[i][j], tp[j][i] = P[i][j] for this tile's 32 queries (4 consecutive i per register group)
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+    if (t <= wave) {
+#pragma unroll
+      for (int g = 0; g < 4; ++g) {
+        union { bf16 e[4]; u32x2 u; } ks, kp;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int r = 4 * g + e;
+          ks.e[e] = f2bf(p[t][r] * (dp[t][r] - tt[r]));
+          kp.e[e] = f2bf(p[t][r]);
+        }
+        const int off = (32 * t + jl) * PT + (32 * wave + 8 * g + 4 * (lane >> 5)) * 2;
+        *(u32x2*)(S.ts + off) = ks.u;
+        *(u32x2*)(S.tp + off) = kp.u;
+      }
+    }
+}
+
+// backward, second part: dK, dV of key tile W (the 16-query steps s >= 2 W) and dQ of query tile W (the 16-key steps s < 2 W + 2)
+template <int NT, int W>
+DEV void almc_bwd_grads(bf16* ob, const AlmCausalBwdSmem<NT>& S, int L, int H, int lane) {
+  constexpr int PT = AlmCausalBwdSmem<NT>::PT;
+  const size_t ld = (size_t)3 * H * 64;
+  const int Lq = L - 32 * W, jl = lane & 31;
+#pragma unroll
+  for (int db = 0; db < 2; ++db) {
+    f32x16 dv, dk, dq;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { dv[r] = 0.f; dk[r] = 0.f; dq[r] = 0.f; }
+#pragma unroll
+    for (int s = 2 * W; s < 2 * NT; ++s) {
+      Chunk16 bp, bs;
+      const int off = (32 * W + jl) * PT + (16 * s + 8 * (lane >> 5)) * 2;
+      bp.u = *(const u32x4*)(S.tp + off);
+      bs.u = *(const u32x4*)(S.ts + off);
+      dv = mfma32_bf16(am_frag_tr<AM_PI>(S.d, db * 32, s, lane), bp.h, dv);      // dV^T[d][j] = sum_i dO^T[d][i] P[i][j]
+      dk = mfma32_bf16(am_frag_tr<AM_PI>(S.q, db * 32, s, lane), bs.h, dk);      // dK^T[d][j] = sum_i Q^T[d][i] dS[i][j]
+    }
+#pragma unroll
+    for (int s = 0; s < 2 * W + 2; ++s)
+      dq = mfma32_bf16(am_frag_tr<AM_PI>(S.k, db * 32, s, lane), am_frag_tr<PT>(S.ts, 32 * W, s, lane), dq);   // dQ^T[d][i] = sum_j K^T[d][j] dS^T[j][i]
+    am_store_T(ob + 2 * H * 64, ld, Lq, db * 32, dv, 1.f, lane);
+    am_store_T(ob + H * 64, ld, Lq, db * 32, dk, 0.125f, lane);
+    am_store_T(ob, ld, Lq, db * 32, dq, 0.125f, lane);
+  }
+}
+
+template <int NT>
+__global__ __launch_bounds__(64 * NT) void attention_causal_long_mfma_bwd_kernel(const bf16* qkv, const int64_t* mask, const bf16* dctx, bf16* dqkv, int B, int L,
+                                                                                  int H) {
+  __shared__ __attribute__((aligned(16))) AlmCausalBwdSmem<NT> S;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int bh = blockIdx.x, b = bh / H, h = bh % H;
+  const size_t ld = (size_t)3 * H * 64, ldc = (size_t)H * 64;
+  const bf16* qb = qkv + (size_t)b * L * ld + h * 64;
+  const bf16* dob = dctx + (size_t)b * L * ldc + h * 64;
+  alm_load_image<NT>(qb, ld, L, S.q, tid);
+  alm_load_image<NT>(qb + H * 64, ld, L, S.k, tid);
+  alm_load_image<NT>(dob, ldc, L, S.d, tid);
+  if (tid < 32 * NT) S.madd[tid] = al_madd(mask, b, L, tid);
+  f32x16 p[NT], dp[NT];
+  switch (wave) {
+    case 0: almc_bwd_scores<NT, 0>(qb, dob, p, dp, L, H, lane); break;
+    case 1: almc_bwd_scores<NT, 1>(qb, dob, p, dp, L, H, lane); break;
+    case 2: if constexpr (NT > 2) almc_bwd_scores<NT, 2>(qb, dob, p, dp, L, H, lane); break;
+    default: if constexpr (NT > 3) almc_bwd_scores<NT, 3>(qb, dob, p, dp, L, H, lane); break;
+  }
+  __syncthreads();
+  almc_bwd_softmax<NT>(p, dp, S, L, wave, lane);
+  __syncthreads();
+  bf16* ob = dqkv + ((size_t)b * L + 32 * wave) * ld + h * 64;      // key tile `wave` for dK, dV; query tile `wave` for dQ
+  switch (wave) {
+    case 0: almc_bwd_grads<NT, 0>(ob, S, L, H, lane); break;
+    case 1: almc_bwd_grads<NT, 1>(ob, S, L, H, lane); break;
+    case 2: if constexpr (NT > 2) almc_bwd_grads<NT, 2>(ob, S, L, H, lane); break;
+    default: if constexpr (NT > 3) almc_bwd_grads<NT, 3>(ob, S, L, H, lane); break;
+  }
+}
+
+// ---- the CLIP text tower's streaming pieces
+// x[row] = token_embedding[ids[row]] + positional_embedding[row % L]: embed_fwd_kernel without the token-type row (and no LayerNorm behind it)
+template <typename T>
+__global__ __launch_bounds__(256) void embed_clip_fwd_kernel(const int64_t* ids, const T* word, const T* pos, T* out, int M, int L, int C, int vocab) {
+  const int nchunk = C / 8;
+  size_t total = (size_t)M * nchunk;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    int c = (int)(i % nchunk);
+    int row = (int)(i / nchunk);
+    int64_t id = ids[row];
+    if (id < 0) id = 0;
+    if (id >= vocab) id = vocab - 1;
+    float a[8], b[8];
+    load8(word + (size_t)id * C + c * 8, a);
+    load8(pos + (size_t)(row % L) * C + c * 8, b);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) a[e] += b[e];
+    store8(out + (size_t)row * C + c * 8, a);
+  }
+}
+// End-of-text pooling by the mask: idx[b] = (ones in mask[b]) - 1, clamped into the caption; out[b] = x[b][idx[b]]. A thread owns one 8-column
+// chunk of one sample and counts that sample's mask itself (L <= 128 cached words); the thread of chunk 0 stores idx[b].
+template <typename T>
+__global__ __launch_bounds__(256) void last_token_gather_kernel(const T* x, const int64_t* mask, T* out, int32_t* idx, int B, int L, int C) {
+  const int nchunk = C / 8;
+  const size_t total = (size_t)B * nchunk;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int c = (int)(i % nchunk), b = (int)(i / nchunk);
+    int n = 0;
+    for (int l = 0; l < L; ++l) n += mask[(size_t)b * L + l] != 0 ? 1 : 0;
+    int r = n - 1;
+    if (r < 0) r = 0;
+    float v[8];
+    load8(x + ((size_t)b * L + r) * C + c * 8, v);
+    store8(out + (size_t)b * C + c * 8, v);
+    if (c == 0) idx[b] = r;
+  }
+}
+// dx[b][idx[b]] = d[b]; the other rows of dx are left as they are (the caller zeroes them)
+template <typename T>
+__global__ __launch_bounds__(256) void last_token_scatter_kernel(const T* d, const int32_t* idx, T* dx, int B, int L, int C) {
+  const int nchunk = C / 8;
+  const size_t total = (size_t)B * nchunk;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const int c = (int)(i % nchunk), b = (int)(i / nchunk);
+    int r = idx[b];
+    if (r < 0) r = 0;
+    if (r >= L) r = L - 1;
+    float v[8];
+    load8(d + (size_t)b * C + c * 8, v);
+    store8(dx + ((size_t)b * L + r) * C + c * 8, v);
+  }
+}
+
 // BertPooler backward through tanh: out = dy * (1 - y^2)
 template <typename T>
 __global__ __launch_bounds__(256) void tanh_bwd_kernel(const T* dy, const T* y, T* out, size_t n8) {
@@ -1389,6 +2036,70 @@ extern "C" int clite_mean_pool_bwd(int dtype, const void* dy, const int64_t* mas
   DISPATCH(dtype,
            hipLaunchKernelGGL(mean_pool_bwd_kernel<bf16>, dim3(grid), dim3(256), 0, st, (const bf16*)dy, mask, inv, (bf16*)dh, B, L, C),
            hipLaunchKernelGGL(mean_pool_bwd_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)dy, mask, inv, (float*)dh, B, L, C));
+  return (int)hipGetLastError();
+}
+
+extern "C" int clite_attention_causal_fwd(int dtype, const void* qkv, const int64_t* mask, void* ctx, int B, int L, int H, void* stream) {
+  if (B <= 0 || L < 1 || L > AL_L || H <= 0 || !qkv || !ctx) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  if (L > AT_L) {      // 33..128: one workgroup per (batch, head), a wave per 32-query tile over the key tiles up to its own
+#define ALC_FWD(NT) hipLaunchKernelGGL(attention_causal_long_mfma_fwd_kernel<NT>, dim3(B * H), dim3(64 * NT), 0, st, (const bf16*)qkv, mask, (bf16*)ctx, B, L, H)
+    DISPATCH(dtype,
+             if (L <= 64) ALC_FWD(2); else if (L <= 96) ALC_FWD(3); else ALC_FWD(4),
+             hipLaunchKernelGGL(attention_causal_long_fwd_kernel<float>, dim3(B * H), dim3(256), 0, st, (const float*)qkv, mask, (float*)ctx, B, L, H));
+#undef ALC_FWD
+    return (int)hipGetLastError();
+  }
+  DISPATCH(dtype,
+           hipLaunchKernelGGL(attention_causal_mfma_fwd_kernel, dim3((B * H + 3) / 4), dim3(256), 0, st, (const bf16*)qkv, mask, (bf16*)ctx, B, L, H),
+           hipLaunchKernelGGL(attention_causal_fwd_kernel<float>, dim3(B * H), dim3(64), 0, st, (const float*)qkv, mask, (float*)ctx, B, L, H));
+  return (int)hipGetLastError();
+}
+
+extern "C" int clite_attention_causal_bwd(int dtype, const void* qkv, const int64_t* mask, const void* dctx, void* dqkv, int B, int L, int H, void* stream) {
+  if (B <= 0 || L < 1 || L > AL_L || H <= 0 || !qkv || !dctx || !dqkv) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  if (L > AT_L) {
+#define ALC_BWD(NT) hipLaunchKernelGGL(attention_causal_long_mfma_bwd_kernel<NT>, dim3(B * H), dim3(64 * NT), 0, st, (const bf16*)qkv, mask, (const bf16*)dctx, (bf16*)dqkv, B, L, H)
+    DISPATCH(dtype,
+             if (L <= 64) ALC_BWD(2); else if (L <= 96) ALC_BWD(3); else ALC_BWD(4),
+             hipLaunchKernelGGL(attention_causal_long_bwd_kernel<float>, dim3(B * H), dim3(256), 0, st, (const float*)qkv, mask, (const float*)dctx, (float*)dqkv, B, L, H));
+#undef ALC_BWD
+    return (int)hipGetLastError();
+  }
+  DISPATCH(dtype,
+           hipLaunchKernelGGL(attention_causal_mfma_bwd_kernel, dim3((B * H + 1) / 2), dim3(128), 0, st, (const bf16*)qkv, mask, (const bf16*)dctx, (bf16*)dqkv, B, L, H),
+           hipLaunchKernelGGL(attention_causal_bwd_kernel<float>, dim3(B * H), dim3(64), 0, st, (const float*)qkv, mask, (const float*)dctx, (float*)dqkv, B, L, H));
+  return (int)hipGetLastError();
+}
+
+extern "C" int clite_embed_clip_fwd(int dtype, const int64_t* ids, const void* word, const void* pos, void* out, int M, int L, int C, int vocab, void* stream) {
+  if (M <= 0 || L <= 0 || M % L || C <= 0 || C % 8 || vocab <= 0 || !ids || !word || !pos || !out) return -1;
+  int grid = ew_grid((size_t)M * (C / 8));
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype,
+           hipLaunchKernelGGL(embed_clip_fwd_kernel<bf16>, dim3(grid), dim3(256), 0, st, ids, (const bf16*)word, (const bf16*)pos, (bf16*)out, M, L, C, vocab),
+           hipLaunchKernelGGL(embed_clip_fwd_kernel<float>, dim3(grid), dim3(256), 0, st, ids, (const float*)word, (const float*)pos, (float*)out, M, L, C, vocab));
+  return (int)hipGetLastError();
+}
+
+extern "C" int clite_last_token_gather(int dtype, const void* x, const int64_t* mask, void* out, int32_t* idx, int B, int L, int C, void* stream) {
+  if (B <= 0 || L <= 0 || C <= 0 || C % 8 || !x || !mask || !out || !idx) return -1;
+  int grid = ew_grid((size_t)B * (C / 8));
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype,
+           hipLaunchKernelGGL(last_token_gather_kernel<bf16>, dim3(grid), dim3(256), 0, st, (const bf16*)x, mask, (bf16*)out, idx, B, L, C),
+           hipLaunchKernelGGL(last_token_gather_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)x, mask, (float*)out, idx, B, L, C));
+  return (int)hipGetLastError();
+}
+
+extern "C" int clite_last_token_scatter(int dtype, const void* d, const int32_t* idx, void* dx, int B, int L, int C, void* stream) {
+  if (B <= 0 || L <= 0 || C <= 0 || C % 8 || !d || !idx || !dx) return -1;
+  int grid = ew_grid((size_t)B * (C / 8));
+  hipStream_t st = (hipStream_t)stream;
+  DISPATCH(dtype,
+           hipLaunchKernelGGL(last_token_scatter_kernel<bf16>, dim3(grid), dim3(256), 0, st, (const bf16*)d, idx, (bf16*)dx, B, L, C),
+           hipLaunchKernelGGL(last_token_scatter_kernel<float>, dim3(grid), dim3(256), 0, st, (const float*)d, idx, (float*)dx, B, L, C));
   return (int)hipGetLastError();
 }
 

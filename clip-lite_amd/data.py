@@ -54,8 +54,11 @@ def normalize_caption(caption: str, max_caption_length: int = 30) -> str:
 
 def text_framing(model_name: str) -> str:
     """Which tokenizer framing a text tower's name selects — the same test the reference applies to the name (encoder.py:165): "bert" in it
-    means BERT ([CLS] ... [SEP], pad id 0), anything else the MPNet tower (<s> ... </s>, pad id 1)."""
-    return "bert" if "bert" in (model_name or "bert") else "mpnet"
+    means BERT ([CLS] ... [SEP], pad id 0), anything else the MPNet tower (<s> ... </s>, pad id 1). A CLIP text tower ("clip_text*", tested
+    first) takes the BERT framing: WordPiece ids, pad id 0, and [SEP] — the last attended token — in the end-of-text role its pooling reads
+    (CLIP's own BPE tokenizer is a download)."""
+    name = model_name or "bert"
+    return "bert" if name.startswith("clip_text") or "bert" in name else "mpnet"
 
 
 MPNET_VOCAB_SIZE = 30527          # transformers.MPNetConfig().vocab_size

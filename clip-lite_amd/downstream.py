@@ -773,6 +773,8 @@ def _check_bias_eval_model(_A, _C):
         raise SystemExit(f"bias_eval: MODEL.LOSS.TYPE {_C.MODEL.LOSS.TYPE} has no projection heads (loss.global_d.img_block / text_block), which "
                          "carry both towers into the space the direction lives in; the reference's --loss-type concat path never worked either")
     limit = 128 if text_framing(_C.MODEL.TEXTUAL.NETWORK_NAME) == "bert" else 32
+    if _C.MODEL.TEXTUAL.NETWORK_NAME.startswith("clip_text"):          # the CLIP text tower takes what its positional embedding covers
+        limit = int(_C.MODEL.TEXTUAL.CONTEXT_LENGTH)
     if not 1 <= _A.max_length <= limit:
         raise SystemExit(f"bias_eval: --max-length {_A.max_length} exceeds the {limit} tokens of the text tower {_C.MODEL.TEXTUAL.NETWORK_NAME}")
 

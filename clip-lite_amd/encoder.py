@@ -8,6 +8,7 @@ import torch.nn as nn
 
 from . import hip
 from .bert import BertModel, LinearParams, bert_backward, bert_forward
+from .cliptext import SPECS as CLIP_TEXT_SPECS, ClipTextModel, cliptext_backward, cliptext_forward
 from .resnet import ResNet, resnet_backward, resnet_forward
 from .vit import VisionTransformer, vit_backward, vit_forward
 
@@ -133,6 +134,24 @@ class _BertFn(torch.autograd.Function):
         return None, None, None, None, None, None
 
 
+class _ClipTextFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, anchor, enc, rt, input_ids, attention_mask):
+        out, saved = cliptext_forward(rt, enc.strans, input_ids, attention_mask)
+        ctx.enc, ctx.rt, ctx.saved = enc, rt, saved
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        cliptext_backward(ctx.rt, ctx.enc.strans, ctx.saved, dout.contiguous())
+        rt = ctx.rt
+        ev = rt.arena.note_stream_work()     # as _BertFn.backward: consumers of the arena, and the caller's stream, join this node's stream
+        main = getattr(rt, "main_stream", None)
+        if ev is not None and main is not None and main != torch.cuda.current_stream(rt.device):
+            main.wait_event(ev)
+        return None, None, None, None, None
+
+
 class _TransformFn(torch.autograd.Function):
     """optional fc1 -> ReLU -> fc2 head (reference encoder.py:182-185,200-203; TRANSFORM is false in every shipped YAML)"""
 
@@ -171,10 +190,13 @@ class TextEncoder(nn.Module):
     ``pooler_output``; any other name (the reference's "sentence-transformers/paraphrase-mpnet-base-v2") builds the random-init MPNetModel
     (mpnet.py) and returns the masked mean over the token states (reference encoder.py:171-175, 197-198). One deviation on that branch:
     the reference ignores ``num_hidden_layers`` there and always builds MPNetConfig()'s 12 layers; here it is honoured (default 12).
+    A ``model_name`` beginning with "clip_text" (tested first; not in the reference) builds the CLIP text transformer (cliptext.py; "clip_text_b" is
+    the one named size: 77 tokens, 512 wide, 8 heads, 512 output features) and returns the projected end-of-text state; ``txt_enc_dim`` must then
+    be the tower's output width, and ``context_length`` (MODEL.TEXTUAL.CONTEXT_LENGTH) sizes its positional embedding.
     GloVe and pretrained weights need assets or a download that are unavailable and raise."""
 
     def __init__(self, word_dict=None, mode="train_sbert", transform_embedding=False, txt_enc_dim=512, glove_path=None, train_enc=False,
-                 load_glove=True, model_name="bert-base-uncased", pretrained=False, num_hidden_layers=12):
+                 load_glove=True, model_name="bert-base-uncased", pretrained=False, num_hidden_layers=12, context_length=None):
         super().__init__()
         self.transform_embedding = transform_embedding
         self.txt_enc_dim = txt_enc_dim
@@ -187,14 +209,25 @@ class TextEncoder(nn.Module):
             if pretrained:
                 raise RuntimeError(f"pretrained weights of {model_name!r} are a download, which is not available; build the randomly initialised "
                                    "encoder (MODEL.TEXTUAL.PRETRAINED false) and load a state_dict instead")
-            if "bert" in model_name:
+            in_dim = 768
+            if model_name.startswith("clip_text"):
+                if model_name not in CLIP_TEXT_SPECS:
+                    raise ValueError(f"unsupported CLIP text tower {model_name!r}; supported: {sorted(CLIP_TEXT_SPECS)}")
+                ctxlen, width, heads, _, embed = CLIP_TEXT_SPECS[model_name]
+                if txt_enc_dim != embed:
+                    raise ValueError(f"MODEL.TEXTUAL.FEATURE_SIZE is {txt_enc_dim}, but {model_name} produces {embed} features; set "
+                                     f"MODEL.TEXTUAL.FEATURE_SIZE to {embed}")
+                print("Using clip text model with layers: " + str(self.num_hidden_layers))
+                self.strans = ClipTextModel(context_length=ctxlen if context_length is None else context_length, width=width, heads=heads,
+                                            num_hidden_layers=self.num_hidden_layers, embed_dim=embed)
+                in_dim = self.strans.out_dim
+            elif "bert" in model_name:
                 print("Using bert model with layers: " + str(self.num_hidden_layers))
                 self.strans = BertModel(num_hidden_layers=self.num_hidden_layers)
             else:
                 from .mpnet import MPNetModel
                 print("Using mpnet model with layers: " + str(self.num_hidden_layers))
                 self.strans = MPNetModel(num_hidden_layers=self.num_hidden_layers)
-            in_dim = 768
         else:
             raise NotImplementedError(f"text encoder mode {mode!r} needs assets that are not available (GloVe vectors / HF hub)")
         if transform_embedding:
@@ -203,7 +236,13 @@ class TextEncoder(nn.Module):
 
     def forward(self, x):
         rt = _runtime_of(self)
-        if self.mode == "train_sbert":
+        if self.mode == "train_sbert" and self.strans.kind == "clip":          # (no dropout: no seed is drawn)
+            grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.strans.parameters())
+            if grad:
+                x = _ClipTextFn.apply(rt.anchor, self, rt, x["input_ids"], x["attention_mask"])
+            else:
+                x, _ = cliptext_forward(rt, self.strans, x["input_ids"], x["attention_mask"])
+        elif self.mode == "train_sbert":
             step = rt.next_step(self.training)
             grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.strans.parameters())
             if grad:

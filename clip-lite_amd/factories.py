@@ -167,7 +167,7 @@ class TextualHeadFactory(Factory):
             "word_dict": {}, "mode": name, "transform_embedding": _C.MODEL.TEXTUAL.TRANSFORM, "txt_enc_dim": _C.MODEL.TEXTUAL.FEATURE_SIZE,
             "load_glove": _C.MODEL.TEXTUAL.LOAD_GLOVE, "glove_path": _C.MODEL.TEXTUAL.GLOVE_PATH, "train_enc": _C.MODEL.TEXTUAL.TRAIN_EMBEDDINGS,
             "pretrained": _C.MODEL.TEXTUAL.PRETRAINED, "model_name": _C.MODEL.TEXTUAL.NETWORK_NAME,
-            "num_hidden_layers": _C.MODEL.TEXTUAL.NUM_HIDDEN_LAYERS,
+            "num_hidden_layers": _C.MODEL.TEXTUAL.NUM_HIDDEN_LAYERS, "context_length": _C.MODEL.TEXTUAL.CONTEXT_LENGTH,
         }
         return cls.create(name, **kwargs)
 

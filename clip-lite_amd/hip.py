@@ -144,6 +144,11 @@ _SIGNATURES = {
     "clite_embed_mpnet_bwd": [_I, _V, _V, _V, _V, _V, _I, _I, _I, _I, _I, _I, _V],
     "clite_mean_pool_fwd": [_I, _V, _V, _V, _V, _I, _I, _I, _V],
     "clite_mean_pool_bwd": [_I, _V, _V, _V, _V, _I, _I, _I, _V],
+    "clite_attention_causal_fwd": [_I, _V, _V, _V, _I, _I, _I, _V],
+    "clite_attention_causal_bwd": [_I, _V, _V, _V, _V, _I, _I, _I, _V],
+    "clite_embed_clip_fwd": [_I, _V, _V, _V, _V, _I, _I, _I, _I, _V],
+    "clite_last_token_gather": [_I, _V, _V, _V, _V, _I, _I, _I, _V],
+    "clite_last_token_scatter": [_I, _V, _V, _V, _I, _I, _I, _V],
     "clite_tanh_bwd": [_I, _V, _V, _V, _U64, _V],
     "clite_critic_jsd_fwd": [_I, _V, _V, _V, _I, _I, _V, _V, _V, _V],
     "clite_l2_normalize": [_I, _V, _V, _I, _I, _V],
@@ -924,6 +929,38 @@ def mean_pool_bwd(dt, dy, mask, inv, dh, B, L, Cc):
 
 def tanh_bwd(dt, dy, y, out, n):
     check(lib().clite_tanh_bwd(dt, p(dy), p(y), p(out), n, stream_ptr(dy)), "tanh_bwd")
+
+
+# ------------------------------------------------------------------------------------------------ CLIP text pieces (clip_lite_amd/cliptext.py)
+def attention_causal_fwd(dt, qkv, mask, ctx, B, L, H):
+    """attention_fwd in which query i sees the keys j <= i only (and, with a mask, only those it allows; mask[b][0] == 1), without dropout;
+    L <= 128. In bf16 from 33 tokens on, the key tiles above the diagonal are not computed (include/clite.h: clite_attention_causal_fwd)."""
+    check(lib().clite_attention_causal_fwd(dt, p(qkv), p(mask), p(ctx), B, L, H, stream_ptr(qkv)), "attention_causal_fwd")
+
+
+def attention_causal_bwd(dt, qkv, mask, dctx, dqkv, B, L, H):
+    """dqkv of attention_causal_fwd, the probabilities recomputed from qkv; no atomics."""
+    check(lib().clite_attention_causal_bwd(dt, p(qkv), p(mask), p(dctx), p(dqkv), B, L, H, stream_ptr(qkv)), "attention_causal_bwd")
+
+
+def embed_clip_fwd(dt, ids, word, pos, out, M, L, Cc, vocab):
+    """out [M][C] = word[ids] + pos[row % L] (include/clite.h: clite_embed_clip_fwd); its backward is embed_bwd with padding_idx = -1."""
+    assert pos.numel() >= L * Cc and out.numel() == M * Cc and word.dtype == pos.dtype == out.dtype == TORCH_DTYPE[dt]
+    check(lib().clite_embed_clip_fwd(dt, p(ids), p(word), p(pos), p(out), M, L, Cc, vocab, stream_ptr(out)), "embed_clip_fwd")
+
+
+def last_token_gather(dt, x, mask, out, idx, B, L, Cc):
+    """idx int32 [B] = mask.sum(1) - 1; out [B][C] = x[b][idx[b]] of x [B * L][C] (include/clite.h: clite_last_token_gather)."""
+    assert x.numel() == B * L * Cc and out.numel() == B * Cc and x.dtype == out.dtype == TORCH_DTYPE[dt] and x.is_contiguous() and out.is_contiguous()
+    assert mask.dtype == torch.int64 and mask.numel() == B * L and mask.is_contiguous() and idx.dtype == torch.int32 and idx.numel() == B
+    check(lib().clite_last_token_gather(dt, p(x), p(mask), p(out), p(idx), B, L, Cc, stream_ptr(x)), "last_token_gather")
+
+
+def last_token_scatter(dt, d, idx, dx, B, L, Cc):
+    """dx[b][idx[b]] = d[b]; the other rows of dx [B * L][C] stay as they are."""
+    assert dx.numel() == B * L * Cc and d.numel() == B * Cc and d.dtype == dx.dtype == TORCH_DTYPE[dt] and d.is_contiguous() and dx.is_contiguous()
+    assert idx.dtype == torch.int32 and idx.numel() == B
+    check(lib().clite_last_token_scatter(dt, p(d), p(idx), p(dx), B, L, Cc, stream_ptr(d)), "last_token_scatter")
 
 
 # ------------------------------------------------------------------------------------------------ ViT pieces (clip_lite_amd/vit.py)

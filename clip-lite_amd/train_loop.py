@@ -194,8 +194,10 @@ class TrainStep:
         inert = self._inert_params()
         from .loss import GlobalDiscriminatorDot
         from .resnet import ResNet
-        # (the per-phase graphs are scheduled around the ResNet's backward segments; a ViT image encoder takes the whole step as one graph)
+        # (the per-phase graphs are scheduled around the ResNet's backward segments and BERT's: a ViT image encoder, and the CLIP text tower
+        # whatever the image encoder is, take the whole step as one graph)
         return (getattr(m, "mode", None) == "train_sbert" and not m.text_encoder.transform_embedding and m.training
+                and getattr(getattr(m.text_encoder, "strans", None), "kind", "bert") != "clip"
                 and isinstance(getattr(m.image_encoder, "img_encoder", None), ResNet)
                 and isinstance(m.loss.global_d, GlobalDiscriminatorDot)
                 and not getattr(m.image_encoder, "frozen", False)
@@ -742,10 +744,13 @@ def main(_A: argparse.Namespace):
     if dist.is_master_process():
         checkpoint_manager = CheckpointManager(_A.checkpoints_dir + _C.RUN_ID, model=model, optimizer=optimizer, scheduler=scheduler, scaler=scaler)
 
-    # the caption length the step is captured at: the attention kernels' cap, 128 tokens for the BERT tower and 32 for MPNet (bert.bert_forward)
-    text_kind = getattr(getattr(getattr(model, "text_encoder", None), "strans", None), "kind", "bert")
+    # the caption length the step is captured at: the attention kernels' cap, 128 tokens for the BERT tower and 32 for MPNet (bert.bert_forward);
+    # the CLIP text tower's own context length (cliptext.py)
+    strans = getattr(getattr(model, "text_encoder", None), "strans", None)
+    text_kind = getattr(strans, "kind", "bert")
+    cap = strans.context_length if text_kind == "clip" else 128 if text_kind == "bert" else 32
     step = TrainStep(model, optimizer, scheduler, scaler, _C.OPTIM.CLIP_GRAD_NORM, exchange, graph=not _A.no_hip_graph,
-                     pad_to=min(int(_C.DATA.MAX_CAPTION_LENGTH), 128 if text_kind == "bert" else 32), allow_eager_fallback=_A.allow_eager_fallback, defer_update=True)
+                     pad_to=min(int(_C.DATA.MAX_CAPTION_LENGTH), cap), allow_eager_fallback=_A.allow_eager_fallback, defer_update=True)
     for iteration in range(start_iteration + 1, _C.OPTIM.NUM_ITERATIONS + 1):
         if clusters and iteration == _C.DATA.NEGATIVE_SAMPLING_START_ITERATION and loader_type == "normal":      # reference train.py:190-203
             logger.info("Starting clustered negative sampling, loading new dataloaders...")

@@ -487,6 +487,27 @@ int clite_embed_mpnet_bwd(int dtype, const int64_t* ids, const int32_t* pids, co
 int clite_mean_pool_fwd(int dtype, const void* h, const int64_t* mask, void* out, float* inv, int B, int L, int C, void* stream);
 int clite_mean_pool_bwd(int dtype, const void* dy, const int64_t* mask, const float* inv, void* dh, int B, int L, int C, void* stream);
 
+/* ---- CLIP text transformer (open_clip TextTransformer; clip_lite_amd/cliptext.py). Additive to ABI v12; the entry points above are unchanged and
+ * launch what they launched.
+ * Causal self-attention: layouts, head size (64) and scaling (/ 8) of clite_attention_fwd; query i sees key j iff j <= i and (mask == NULL or
+ * mask[b][j] == 1). A key behind the diagonal takes no part in the softmax (its score is -inf, its probability an exact 0); a masked key in
+ * front of it gets clite_attention_fwd's additive finfo.min. PRECONDITION: mask[b][0] == 1 for every sample (every caption has a first token),
+ * so that no query's row is empty; with mask[b][0] == 0 the leading masked keys share the row's weight uniformly, as a fully masked row does
+ * in clite_attention_fwd. No dropout (the tower has none). L <= 32: the one-tile kernels with the test on the tile; 33 <= L <= 128: one workgroup per
+ * (batch, head), a wave per 32-query tile; in bf16 wave w forms only the key tiles 0..w (the products above the diagonal are not computed),
+ * dQ of query tile w sums the key tiles 0..w and dK / dV of key tile w the query tiles w..NT-1 in ascending order. No float atomics, every
+ * output element written once in a fixed order: the same bits on every run in both settings of clite_set_deterministic. Returns -1 and
+ * launches nothing for L > 128, L < 1, a NULL qkv / ctx / dctx / dqkv or an unknown dtype. */
+int clite_attention_causal_fwd(int dtype, const void* qkv, const int64_t* mask, void* ctx, int B, int L, int H, void* stream);
+int clite_attention_causal_bwd(int dtype, const void* qkv, const int64_t* mask, const void* dctx, void* dqkv, int B, int L, int H, void* stream);
+/* Token assembly: out[row] = word[ids[row]] + pos[row % L] (no token types, no LayerNorm); ids clamped into [0, vocab). M = B L rows, C % 8 == 0.
+ * The sum is formed in f32 and rounded once. Backward: clite_embed_bwd with padding_idx = -1 (nn.Embedding without a padding row, as in CLIP). */
+int clite_embed_clip_fwd(int dtype, const int64_t* ids, const void* word, const void* pos, void* out, int M, int L, int C, int vocab, void* stream);
+/* End-of-text pooling by the mask: idx[b] = (number of nonzero mask[b][l]) - 1 (0 for an all-zero mask), out[b] = x[b][idx[b]] of x [B * L][C].
+ * Backward: dx[b][idx[b]] = d[b], the other rows of dx left as they are (the caller zeroes them). Exact copies; C % 8 == 0. */
+int clite_last_token_gather(int dtype, const void* x, const int64_t* mask, void* out, int32_t* idx, int B, int L, int C, void* stream);
+int clite_last_token_scatter(int dtype, const void* d, const int32_t* idx, void* dx, int B, int L, int C, void* stream);
+
 /* BertPooler tanh backward: out = dy * (1 - y^2), n % 8 == 0 */
 int clite_tanh_bwd(int dtype, const void* dy, const void* y, void* out, uint64_t n, void* stream);
 
