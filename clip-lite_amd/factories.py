@@ -11,7 +11,7 @@ from torch import nn
 from . import data as vdata
 from .config import Config
 from .encoder import ImageEncoder, TextEncoder
-from .loss import InfoNCELoss, JSDInfoMaxLoss
+from .loss import InfoNCELoss, JSDInfoMaxLoss, SigLIPLoss
 from .model import VLInfoModel
 from .optim import FusedAdamW, FusedLAMB, FusedLARS, FusedSGD, Lookahead, lr_scheduler
 
@@ -173,7 +173,8 @@ class TextualHeadFactory(Factory):
 
 
 class LossFactory(Factory):
-    PRODUCTS: Dict[str, Callable] = {"jsd": JSDInfoMaxLoss, "infonce": InfoNCELoss}     # "infonce": BASELINE config 4 (not in the reference)
+    # "infonce": BASELINE config 4, "siglip": the pairwise sigmoid loss of Zhai et al. 2023 (neither is in the reference)
+    PRODUCTS: Dict[str, Callable] = {"jsd": JSDInfoMaxLoss, "infonce": InfoNCELoss, "siglip": SigLIPLoss}
 
     @classmethod
     def from_config(cls, config: Config) -> JSDInfoMaxLoss:

@@ -155,6 +155,8 @@ _SIGNATURES = {
     "clite_l2_normalize_bwd": [_I, _V, _V, _V, _V, _I, _I, _V],
     "clite_infonce_fwd": [_V, _I, _I, _V, _V, _V, _V, _V],
     "clite_infonce_bwd": [_I, _V, _I, _I, _V, _V, _V, _V, _F, _V, _I, _V, _V],
+    "clite_siglip_fwd": [_V, _I, _I, _V, _V, _V, _V, _V],
+    "clite_siglip_bwd": [_I, _V, _I, _I, _V, _V, _V, _F, _V, _I, _V, _V, _V, _V],
     "clite_xent_fwd": [_V, _I, _I, _I, _V, _I, _V, _V, _V],
     "clite_xent_bwd": [_I, _V, _I, _I, _I, _I, _V, _V, _V, _V, _V, _I, _V],
     "clite_svm_margin": [_V, _V, _V, _I, _I, _I, _V, _V, _V, _V, _V],
@@ -1058,6 +1060,20 @@ def infonce_fwd(Cm, ld, B, temperature, lse_r, lse_c, acc):
 
 def infonce_bwd(dt, Cm, ld, B, temperature, lse_r, lse_c, gout, scale, dC, ldd, dtemp):
     check(lib().clite_infonce_bwd(dt, p(Cm), ld, B, p(temperature), p(lse_r), p(lse_c), p(gout), scale, p(dC), ldd, p(dtemp), stream_ptr(Cm)), "infonce_bwd")
+
+
+def siglip_fwd(Cm, ld, B, temperature, bias, part, acc):
+    """part: f32 scratch of at least 2 * B floats (row partials; shared with siglip_bwd)."""
+    if part is not None and part.numel() < 2 * B:
+        raise RuntimeError("siglip_fwd: part holds fewer than two floats per row")
+    check(lib().clite_siglip_fwd(p(Cm), ld, B, p(temperature), p(bias), p(part), p(acc), stream_ptr(Cm)), "siglip_fwd")
+
+
+def siglip_bwd(dt, Cm, ld, B, temperature, bias, gout, scale, dC, ldd, part, dtemp, dbias):
+    if part is not None and part.numel() < 2 * B:
+        raise RuntimeError("siglip_bwd: part holds fewer than two floats per row")
+    check(lib().clite_siglip_bwd(dt, p(Cm), ld, B, p(temperature), p(bias), p(gout), scale, p(dC), ldd, p(part), p(dtemp), p(dbias), stream_ptr(Cm)),
+          "siglip_bwd")
 
 
 def xent_fwd(logits, ld, B, C, labels, topk, lse, acc):

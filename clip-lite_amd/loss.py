@@ -90,7 +90,7 @@ class JSDInfoMaxLoss(nn.Module):
         if text_prior:
             self.text_prior_d = PriorDiscriminator(sz=text_dim)
         self._noise = None      # test hook: pins the two rand_like draws (image, text)
-        self.estimator = "jsd"  # cross-modal term: "jsd" (reference loss.py:206-222,254) or "infonce" (InfoNCELoss below)
+        self.estimator = "jsd"  # cross-modal term: "jsd" (reference loss.py:206-222,254), "infonce" (InfoNCELoss) or "siglip" (SigLIPLoss below)
 
     def set_prior_noise(self, image_noise, text_noise):
         """Pin the prior noise (reference loss.py:189,196 draws torch.rand_like(image) then (text)); parity tests only."""
@@ -104,6 +104,8 @@ class JSDInfoMaxLoss(nn.Module):
             # every shipped YAML: dot critic, in-batch negatives, no augmented views — the path the captured train step replays
             total, comps = _JSDLossFn.apply(image_features, text_features, self, rt, rt.next_step(self.training))
         else:
+            if getattr(self, "estimator", "jsd") == "siglip":
+                raise NotImplementedError("SigLIPLoss is defined for the dot critic with in-batch negatives only")
             if getattr(self, "estimator", "jsd") != "jsd":
                 raise NotImplementedError("InfoNCELoss is defined for the dot critic with in-batch negatives only")
             if (neg_image_features is None) != (neg_text_features is None):
@@ -123,6 +125,29 @@ class InfoNCELoss(JSDInfoMaxLoss):
     def __init__(self, *a, **k):
         super().__init__(*a, **k)
         self.estimator = "infonce"
+
+
+class SigLIPLoss(JSDInfoMaxLoss):
+    """Pairwise sigmoid loss of SigLIP (Zhai et al. 2023, "Sigmoid Loss for Language Image Pre-Training", Algorithm 1; the reference has no such
+    code). Same projection heads and prior discriminators as JSDInfoMaxLoss; the cross-modal term treats every image-caption pair of the batch as
+    its own binary problem over x_ij = exp(temperature) * <normalize(img_block(I_i)), normalize(text_block(T_j))> + bias:
+    L = 1/B sum_ij softplus(-z_ij x_ij), z = +1 on the diagonal, -1 off it. Nothing is normalised over the batch. `global_d.bias` is a learnable
+    scalar this class alone has; it starts at -10 and the temperature at log 10, the paper's initial values, which balance the B^2 - B negatives
+    against the B positives at the start. Dot critic, in-batch negatives, B a multiple of 8 (csrc/siglip_ops.hip between the cosine GEMM and its
+    two gradient GEMMs).
+
+    Under data parallel the negatives are the other captions / images of the LOCAL batch and the loss is normalised by the local B; the gradients
+    of temperature and bias travel in the flat arena like every other. The paper's multi-device variant, which rotates caption chunks between
+    devices so that every pair of the global batch is seen, is not implemented."""
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        if self.type != "dot":
+            raise ValueError(f"SigLIPLoss needs the dot critic (MODEL.LOSS.TYPE: dot), got {self.type!r}: the loss is defined on the cosines of "
+                             "the two projection heads")
+        self.estimator = "siglip"
+        self.global_d.bias = nn.Parameter(torch.ones([]) * -10.0)
+        self.global_d.temperature.data.fill_(float(np.log(10.0)))
 
 
 def _runtime_of(module):
@@ -296,6 +321,41 @@ def prior_backward(rt, pd, ctx, gout, scale, dfeat_residual, defer=None):
     return dfeat
 
 
+def siglip_critic_fwd(rt, gd, f1, f2, acc):
+    """The SigLIP critic on the projections f1, f2 [B][U]: l2_normalize -> gemm_nt (f32 cosines) -> siglip_fwd; acc[0] += the loss (acc: the
+    step's accumulators, clite_loss_finalize). Returns what siglip_critic_bwd needs: the normalised rows, the cosines and the row-partial scratch
+    (the sigmoid terms themselves are recomputed from the cosines)."""
+    dt = rt.dt
+    B, U = f1.shape
+    if B % 8:
+        raise RuntimeError("SigLIPLoss needs a batch that is a multiple of 8 (GEMM column granularity)")
+    a, b = _alloc(rt, B, U), _alloc(rt, B, U)
+    hip.l2_normalize(dt, f1, a, B, U)
+    hip.l2_normalize(dt, f2, b, B, U)
+    Cm = torch.empty(B, B, device=rt.device, dtype=torch.float32)
+    hip.gemm_nt(dt, a, b, B, B, U, hip.epilogue(Cm, B, out_f32=True))          # all-pairs cosines on the MFMA engine
+    part = torch.empty(2 * B, device=rt.device, dtype=torch.float32)
+    hip.siglip_fwd(Cm, B, B, gd.temperature, gd.bias, part, acc)
+    return (a, b, Cm, part)
+
+
+def siglip_critic_bwd(rt, gd, f1, f2, work, gout, scale, out=None):
+    """siglip_bwd -> gemm_nn / gemm_tn -> l2_normalize_bwd. Returns (df1, df2) in the compute dtype (written into `out` when given); the gradients of
+    temperature and bias accumulate into their arena slots."""
+    dt, A = rt.dt, rt.arena
+    B, U = f1.shape
+    a, b, Cm, part = work
+    df1, df2 = out if out is not None else (_alloc(rt, B, U), _alloc(rt, B, U))
+    dC = _alloc(rt, B, B)
+    hip.siglip_bwd(dt, Cm, B, B, gd.temperature, gd.bias, gout, scale, dC, B, part, A.g(gd.temperature).view(1), A.g(gd.bias).view(1))
+    da, db = _alloc(rt, B, U), _alloc(rt, B, U)
+    hip.gemm_nn(dt, dC, b, B, U, B, hip.epilogue(da, U))                        # da = dC  b
+    hip.gemm_tn(dt, dC, a, B, U, B, hip.epilogue(db, U))                        # db = dC^T a
+    hip.l2_normalize_bwd(dt, f1, a, da, df1, B, U)
+    hip.l2_normalize_bwd(dt, f2, b, db, df2, B, U)
+    return df1, df2
+
+
 def jsd_forward(rt, mod, img, txt, step):
     """image/text features -> (out f32[4] = [total, cross, prior, 0], saved state for jsd_backward). No autograd involved: the
     autograd Function below and the captured multi-graph step (train_loop.TrainStep) both drive the heads through this pair."""
@@ -317,7 +377,9 @@ def jsd_forward(rt, mod, img, txt, step):
     if training:
         rt.bump_counters("loss", 2)
     U = gd.img_block.units
-    if getattr(mod, "estimator", "jsd") == "infonce":
+    if getattr(mod, "estimator", "jsd") == "siglip":
+        work = siglip_critic_fwd(rt, gd, f1, f2, acc)
+    elif getattr(mod, "estimator", "jsd") == "infonce":
         if B % 8:
             raise RuntimeError("InfoNCELoss needs a batch that is a multiple of 8 (GEMM column granularity)")
         a, b = _alloc(rt, B, U), _alloc(rt, B, U)
@@ -344,7 +406,9 @@ def jsd_backward(rt, mod, saved, gout):
     gd = mod.global_d
     U = gd.img_block.units
     df1, df2 = _alloc(rt, B, U), _alloc(rt, B, U)
-    if getattr(mod, "estimator", "jsd") == "infonce":
+    if getattr(mod, "estimator", "jsd") == "siglip":
+        siglip_critic_bwd(rt, gd, f1, f2, work, gout, 1.0 - mod.prior_weight, out=(df1, df2))
+    elif getattr(mod, "estimator", "jsd") == "infonce":
         a, b, Cm, lse = work
         dC = _alloc(rt, B, B)
         hip.infonce_bwd(dt, Cm, B, B, gd.temperature, lse[0], lse[1], gout, 1.0 - mod.prior_weight, dC, B, A.g(gd.temperature).view(1))
@@ -399,14 +463,19 @@ def jsd_half_block(rt, mod, feat, which, step):
 
 
 def jsd_join(rt, mod, hi, ht, acc, gout):
-    """Critic forward, the total, critic backward (JSD estimator, or the InfoNCE all-pairs variant). Returns (out f32[8], df_image, df_text)."""
+    """Critic forward, the total, critic backward (JSD estimator, the InfoNCE all-pairs variant or the SigLIP pairwise sigmoid). Returns
+    (out f32[8], df_image, df_text)."""
     dt, A = rt.dt, rt.arena
     gd = mod.global_d
     f1, f2 = hi["f"], ht["f"]
     B, U = f1.shape[0], gd.img_block.units
     out = torch.empty(8, device=rt.device, dtype=torch.float32)
     df1, df2 = _alloc(rt, B, U), _alloc(rt, B, U)
-    if getattr(mod, "estimator", "jsd") == "infonce":
+    if getattr(mod, "estimator", "jsd") == "siglip":
+        work = siglip_critic_fwd(rt, gd, f1, f2, acc)
+        hip.loss_finalize(acc, mod.prior_weight, out)
+        siglip_critic_bwd(rt, gd, f1, f2, work, gout, 1.0 - mod.prior_weight, out=(df1, df2))
+    elif getattr(mod, "estimator", "jsd") == "infonce":
         if B % 8:
             raise RuntimeError("InfoNCELoss needs a batch that is a multiple of 8 (GEMM column granularity)")
         a, b = _alloc(rt, B, U), _alloc(rt, B, U)

@@ -531,6 +531,16 @@ int clite_infonce_fwd(const float* C, int ld, int B, const float* temperature, f
 /* dC (call dtype, [B][ldd], ldd % 8 == 0, padding columns zeroed) = dL/dC; dtemp (f32 scalar) += ; scale = (1 - prior_weight). */
 int clite_infonce_bwd(int dtype, const float* C, int ld, int B, const float* temperature, const float* lse_r, const float* lse_c,
                       const float* gout, float scale, void* dC, int ldd, float* dtemp, void* stream);
+/* SigLIP pairwise sigmoid variant of the cross-modal term (Zhai et al. 2023, Algorithm 1; csrc/siglip_ops.hip) on the same C f32 [B][ld]
+ * (columns >= B are padding and enter nothing): x_ij = exp(temperature) * C[i][j] + bias, z_ij = +1 on the diagonal and -1 off it,
+ * acc[0] += 1/B sum_ij softplus(-z_ij x_ij); acc[1] is left alone (clite_loss_finalize is shared). Nothing is kept for backward.
+ * part: caller-provided f32 scratch of at least 2 B floats. The row kernels store one partial per row there and a one-wave launch folds them in
+ * a fixed order: no float atomics, the same bits in every run with or without the deterministic mode. */
+int clite_siglip_fwd(const float* C, int ld, int B, const float* temperature, const float* bias, float* part, float* acc, void* stream);
+/* dC (call dtype, [B][ldd], ldd % 8 == 0, padding columns zeroed) = dL/dC, recomputed from C; dtemp, dbias (f32 scalars, either may be NULL) += ;
+ * scale = (1 - prior_weight). */
+int clite_siglip_bwd(int dtype, const float* C, int ld, int B, const float* temperature, const float* bias, const float* gout, float scale,
+                     void* dC, int ldd, float* part, float* dtemp, float* dbias, void* stream);
 /* gout: device scalar dL/d(total); scale = (1 - prior_weight). df1/df2 in dtype; dtemp (f32 scalar) += . neg as in the forward call,
  * neg_inv its inverse permutation (both NULL = roll by one). */
 int clite_critic_jsd_bwd(int dtype, const void* f1, const void* f2, const float* temperature, const float* work, const float* gout, float scale,
